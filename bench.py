@@ -39,11 +39,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  This process holds more streams
-# than that (torch's, one per solver handle, two per split batch, one per batch in flight), and two streams that land on one
-# queue run one after the other: the B = 8192 leg then takes 29.8 ms instead of 22.0 (its two sub-batches serialised).
-# Set before the runtime starts; a value already in the environment wins.  `value`'s own region uses one stream.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# HIP multiplexes a process's streams onto a fixed number of hardware queues (its default, 4).  This process holds more streams
+# than that (torch's, one per solver handle, two per split batch, one per batch in flight); the bench leaves the runtime's queue
+# count as the environment sets it.  `value`'s own region uses one stream.
 
 FP64_PEAK_TFLOPS = 78.6  # MI355X fp64 vector = matrix peak (AMD CDNA4 datasheet)
 HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md: HBM3E 8 TB/s
@@ -317,6 +315,24 @@ def sharded_c_abi_leg(args, g_cost_host):
             pass
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write the last timed step's results as <path>/<name>.npy, float64.  Arrays with one row per problem
+    (the first axis) are cut to a fixed, seeded sample of rows when all of them would not fit DUMP_LIMIT_BYTES; the rows taken
+    are written as `rows.npy` (all of them when nothing was cut), so two runs with the same arguments are compared row for row."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[0].nbytes for a in arrays.values()) + 8
+    keep = min(n, DUMP_LIMIT_BYTES // row_bytes)
+    rows = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a[rows])
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+
+
 def usable_cores():
     """hardware threads this process may actually use: the affinity mask cut by the cgroup's CPU quota (a GPU box hands a one-GPU
     job 16 of the host's cores; os.cpu_count() reports all of them)"""
@@ -421,6 +437,9 @@ def main():
     ap.add_argument("--no-profile", action="store_true", help="diagnostic: no HIP events around the kernels (roofline = null)")
     ap.add_argument("--no-sharded-c-abi", action="store_true", help="N > 1: skip the extra measurement of the same step through qilqr_solve_batch_sharded_device "
                                                                    "(one process, N devices, the library's own RCCL gather; never part of value)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (trajectories, costs, status, iterations, passes; "
+                         "N > 1: the trajectories and costs gathered on rank 0) as DIR/<name>.npy in float64, at most 64 MB in all")
     ap.add_argument("--leg", default="", help=argparse.SUPPRESS)  # internal: a leg bench.py runs in a child process of rank 0 ("sharded-c-abi")
     ap.add_argument("--leg-out", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -578,6 +597,13 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     prof = solver.profile_get()
+    if args.dump_outputs and rank == 0:  # (before the legs below reuse the output buffers)
+        last = (step_no[0] - 1) & 1
+        if world > 1 or rehearse:
+            dump_outputs(args.dump_outputs, dict(traj=g_traj.cpu().numpy(), cost=g_cost.cpu().numpy()))
+        else:
+            dump_outputs(args.dump_outputs, dict(traj=out_traj[last].cpu().numpy(), cost=out_cost[last].cpu().numpy(),
+                                                 **{n: t.cpu().numpy() for n, t in zip(("status", "iters", "n_bwd", "n_fwd"), out_i)}))
 
     # the gather on its own (after the timed region): every rank's shard of the last step to rank 0, waited for
     gather_ms = None
@@ -698,7 +724,7 @@ def main():
                                          for k in ("backward", "rollout", "solve")},
             }
         # ---- the extra legs (never `value`).  HIP hands hardware queues to streams in the order the streams are created and does
-        # not give a destroyed stream's place back, and GPU_MAX_HW_QUEUES = 8: host_to_host is measured FIRST and on `value`'s own
+        # not give a destroyed stream's place back, and their number is fixed: host_to_host is measured FIRST and on `value`'s own
         # handle (one more stream: its copy-back's), then the B = 8192 solver creates its five (streams three to eight of the
         # process: behind further handles they end up sharing queues -- 385 000 instead of 444 000-460 000 solves/s in round 3; and a
         # fresh host_to_host handle BEHIND them read + 0.60 ms over the device-resident call instead of + 0.43, round 6).
@@ -712,7 +738,7 @@ def main():
                         **{k: capi.host_array((B,), np.int32) for k in ("status", "iters", "n_bwd", "n_fwd")})
             # On `value`'s own handle, its event timing switched off (the profile of the timed region was read above): a fresh handle's two
             # streams (its own and the copy-back's) would be the ninth and tenth of the process behind the B = 8192 solver's five, and HIP
-            # multiplexes streams onto GPU_MAX_HW_QUEUES = 8 hardware queues -- round 6 measured + 0.60 ms over the device-resident call with
+            # multiplexes streams onto a fixed number of hardware queues -- round 6 measured + 0.60 ms over the device-resident call with
             # the fresh handle behind the large solver and + 0.43 without the large solver in the process: a collision of the bench's own
             # making, not the library's (profiles/microbench/h2h_ab.py: + 0.33-0.36 in a process of its own).
             solver.profile_mode(0)

@@ -1081,7 +1081,7 @@ int auto_parts(const qilqr_solver *s, long B) {
   // SIMDs with another part's kernels only slows both (B = 1024, round 3: 194k solves/s on one stream, 168k on two,
   // 153k on four); from 4096 on two parts gain 4-5%.  Between 4096 and 16384 FOUR parts are better still when
   // every part's stream has a hardware queue of its own -- GPU_MAX_HW_QUEUES=8 in the environment before the runtime
-  // starts (bench.py sets it): 5120: 366k against 356k solves/s, 6144: 403k / 377k, 7168: 437k / 406k,
+  // starts: 5120: 366k against 356k solves/s, 6144: 403k / 377k, 7168: 437k / 406k,
   // 8192: 461k / 429k, 10240: 441k / 424k, 12288: 472k / 460k; level at 4096, 16384 and 65536; with HIP's default four queues
   // the parts collide with each other and with the caller's streams and two are the safer choice.
   // Round 4 (compaction, k_backward4 and k_rollout3 at every size beyond 4096): four parts are ahead at 16384 and 65536 as well

@@ -1,18 +1,22 @@
 """bench.py's output contract (task statement): one JSON line on rank 0 with the agreed keys, the roofline of
 the dominant kernel measured live, and the CPU baseline at N = 1.  Runs the real script on the GPU, short."""
+import importlib.util
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
-def test_bench_prints_one_json_line_with_the_contract_keys():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+def test_bench_prints_one_json_line_with_the_contract_keys(tmp_path):
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(dump)],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -59,6 +63,35 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert lb["value"] > j["value"] and lb["status_counts"][2] == 0 and lb["status_counts"][3] == 0
     for k in ("k_backward", "k_rollout"):
         assert lb["kernels"][k]["avg_launch_us"] > 1.0 and 0 < lb["kernels"][k]["fp64_frac"] < 1 and 0 < lb["kernels"][k]["hbm_frac"] < 1
+    # --dump-outputs: the last timed step's results, float64, every problem (1024 x 100 knots fits the limit), the same
+    # solve the line's status and iteration counts describe
+    d = {n: np.load(dump / (n + ".npy")) for n in ("traj", "cost", "status", "iters", "n_bwd", "n_fwd", "rows")}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert d["traj"].shape == (1024, 100, 18) and d["cost"].shape == (1024,) and (d["rows"] == np.arange(1024)).all()
+    assert np.isfinite(d["traj"]).all() and (d["cost"] > 0).all()
+    assert np.bincount(d["status"].astype(np.int64), minlength=4).tolist() == j["status_counts"]
+    assert d["iters"].max() == j["iters_max"] and abs(d["iters"].mean() - j["iters_mean"]) < 1e-9
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 << 20
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path):  # (no GPU needed: runs in the CPU suite)
+    """bench.py --dump-outputs: a batch whose results exceed 64 MB is cut to the same seeded rows every time, float64"""
+    spec = importlib.util.spec_from_file_location("bench_for_dump_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    B = 8192
+    arrays = dict(traj=np.arange(B * 100 * 18, dtype=np.float64).reshape(B, 100, 18), cost=np.arange(B, dtype=np.float64),
+                  status=np.arange(B, dtype=np.int32) % 4)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), arrays)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("traj", "cost", "status", "rows")}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in ("traj", "cost", "status", "rows")}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    rows = a["rows"].astype(np.int64)
+    assert 0 < len(rows) < B and (np.diff(rows) > 0).all()
+    assert np.array_equal(a["cost"], rows) and np.array_equal(a["traj"], arrays["traj"][rows]) and np.array_equal(a["status"], rows % 4)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
 
 
 @pytest.mark.gpu

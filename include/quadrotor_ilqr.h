@@ -45,6 +45,7 @@ extern "C" {
 #define QILQR_STATUS_CONVERGED 1          /* ilqr.hh:82-84 */
 #define QILQR_STATUS_MAX_ITERS 2          /* ilqr.hh:86    */
 #define QILQR_STATUS_LINE_SEARCH_FAILED 3 /* ilqr.hh:191-193 */
+#define QILQR_STATUS_QP_FAILED 4          /* extension (qilqr_set_control_limits): a knot's box QP broke down; the iterate is kept */
 
 /* QuadrotorModel constructor arguments: quadrotor_model.hh:7-9, binding.cc:20-23 */
 typedef struct {
@@ -289,6 +290,20 @@ int qilqr_set_regularisation(qilqr_solver *s, double mu_init, double mu_factor, 
  * trajectory rollout, the one-wavefront backward pass over dense Jacobian records -- not on the tuned Euler path. */
 int qilqr_set_integrator(qilqr_solver *s, int32_t integrator);
 
+/* Per-rotor thrust limits -- an EXTENSION (control-limited DDP, Tassa, Mansard & Todorov, ICRA 2014): lo[4], hi[4] bound u0..u3 (N);
+ * +-inf leaves a side open.  Every knot of the backward pass solves the box QP  min 1/2 du^T Q_uu du + Q_u^T du  subject to
+ * lo - u_i <= du <= hi - u_i  by projected Newton (quadrotorilqr_amd/csrc/box_qp.h); the feedback gain has zero rows for the rotors at a
+ * bound, and the value function takes the full updates.  The rollout clamps every control to [lo, hi] after the control law (so an
+ * initial guess outside the box becomes feasible in the first rollout).  Applies to every computing entry point of the handle: the
+ * solves, qilqr_backwards_pass, qilqr_forward_sim, qilqr_line_search (a sharded handle: one call per shard, qilqr_sharded_solver).
+ * Runs on the one-wavefront backward kernel and the lane-per-trajectory rollout, with either integrator and with restarts.
+ * A problem whose QP breaks down at some knot (a pivot <= 0: numerical only, Q_uu stays positive definite when R is) ends with
+ * QILQR_STATUS_QP_FAILED on its current iterate.
+ * QILQR_ERR_INVALID_ARG unless lo[a] < hi[a] and neither is NaN for every rotor, and for a mixed-precision handle, non-symmetric
+ * Q or R (or force_general = 1), or R that is not positive definite; a solve with persistent = 1 is refused while limits are set.
+ * lo = hi = NULL clears the limits: every result is then again the handle's without them.  Waits for the handle's stream. */
+int qilqr_set_control_limits(qilqr_solver *s, const double *lo, const double *hi);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -398,7 +413,7 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
 
 /* ABI version of this header: 7 (qilqr_device_config grew by round_launch, rounds_per_launch, fuse_in_flight, dense_weights -- the
  * switches that were environment variables -- and the *_sized entry points carry the caller's structure size; version 6 added
- * `compaction`) */
+ * `compaction`).  qilqr_set_control_limits and QILQR_STATUS_QP_FAILED were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

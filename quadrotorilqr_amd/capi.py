@@ -31,13 +31,14 @@ STATUS_CONVERGED_EXPECTED = 0
 STATUS_CONVERGED = 1
 STATUS_MAX_ITERS = 2
 STATUS_LINE_SEARCH_FAILED = 3
+STATUS_QP_FAILED = 4  # extension: a knot's box QP broke down (set_control_limits)
 
 # every symbol include/quadrotor_ilqr.h declares
 EXPORTS = (
     "qilqr_create", "qilqr_create_sized", "qilqr_destroy", "qilqr_last_error", "qilqr_solve", "qilqr_solve_batch",
     "qilqr_solve_batch_device", "qilqr_cost_trajectory", "qilqr_backwards_pass", "qilqr_forward_sim",
     "qilqr_line_search", "qilqr_cost_history", "qilqr_profile_reset", "qilqr_profile_get", "qilqr_profile_mode", "qilqr_set_regularisation",
-    "qilqr_set_integrator",
+    "qilqr_set_integrator", "qilqr_set_control_limits",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -98,6 +99,7 @@ def load():
         lib.qilqr_sharded_set_transport.argtypes = [C.c_void_p, C.c_int32]
         lib.qilqr_sharded_transport.argtypes = [C.c_void_p]
         lib.qilqr_sharded_transport.restype = C.c_char_p
+        lib.qilqr_set_control_limits.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = lib
     return _lib
 
@@ -382,6 +384,20 @@ class QuadrotorILQRBatch:
         if rc:
             _raise(rc)
 
+    def set_control_limits(self, lo, hi):
+        """Per-rotor thrust limits lo <= u_a <= hi (N; scalars or four values, +-inf leaves a side open) -- an extension: box-constrained
+        iLQR, see qilqr_set_control_limits in include/quadrotor_ilqr.h.  clear_control_limits() switches it off again."""
+        lo = _d(np.broadcast_to(np.asarray(lo, dtype=np.float64), (4,)))
+        hi = _d(np.broadcast_to(np.asarray(hi, dtype=np.float64), (4,)))
+        rc = load().qilqr_set_control_limits(self._h, _p(lo), _p(hi))
+        if rc:
+            _raise(rc)
+
+    def clear_control_limits(self):
+        rc = load().qilqr_set_control_limits(self._h, None, None)
+        if rc:
+            _raise(rc)
+
     def profile_get(self):
         p = Profile()
         rc = load().qilqr_profile_get(self._h, C.byref(p))
@@ -444,6 +460,21 @@ class QuadrotorILQRSharded:
             _raise(rc)
         return out
 
+
+    def set_control_limits(self, lo, hi):
+        """QuadrotorILQRBatch.set_control_limits on every shard's solver"""
+        lo = _d(np.broadcast_to(np.asarray(lo, dtype=np.float64), (4,)))
+        hi = _d(np.broadcast_to(np.asarray(hi, dtype=np.float64), (4,)))
+        for r in range(len(self.devices)):
+            rc = load().qilqr_set_control_limits(load().qilqr_sharded_solver(self._h, C.c_int32(r)), _p(lo), _p(hi))
+            if rc:
+                _raise(rc)
+
+    def clear_control_limits(self):
+        for r in range(len(self.devices)):
+            rc = load().qilqr_set_control_limits(load().qilqr_sharded_solver(self._h, C.c_int32(r)), None, None)
+            if rc:
+                _raise(rc)
 
     TRANSPORTS = {"auto": 0, "rccl": 1, "peer_copy": 2}
 

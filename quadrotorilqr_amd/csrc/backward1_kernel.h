@@ -5,16 +5,37 @@
 #pragma once
 
 #include "backward_common.h"
+#include "box_qp.h"
 
 namespace qilqr {
+
+// arm_line_search (kernels_common.h) for the box form: a QP that failed at any knot ends the problem with QILQR_STATUS_QP_FAILED on
+// its current iterate, without a line search.  The same store pattern (every word stored with a selected VALUE, no complementary
+// branches: kernels_common.h, store_settled).
+__device__ __forceinline__ void arm_line_search_box(const SolveParams &p, const BatchState &st, int b, int iters_now, double cost_now,
+                                                    double QuTk, double kTQuuk, bool qp_failed) {
+  st.prev_cost[b] = cost_now;
+  const bool conv = !qp_failed && iters_now > 0 && is_converged(p, cost_now, cost_now + cost_reduction(QuTk, kTQuuk, 1.0));
+  const bool none = !qp_failed && !conv && iters_now > 0 && p.ls_max_iters <= 0;
+  const bool search = !(qp_failed || conv || none);
+  st.alpha[b] = 1.0;
+  st.trial[b] = 0;
+  if (!search) st.status[b] = qp_failed ? 4 : (conv ? 0 : 3);  // 4: QILQR_STATUS_QP_FAILED
+  st.flags[b] = search ? (F_ACTIVE | F_SEARCH) : 0;
+}
 
 // SYM = true: Q and R are exactly symmetric, so V_xx and H are symmetric to rounding and the
 // accumulator tile can be reused as the next knot's A operand without a transpose; no LDS and no
 // barrier remain in the loop (Q_uu/Q_u are broadcast with DPP row broadcasts, the right-hand sides with
 // ds_bpermute).  SYM = false: general weights, hand-offs go through padded LDS tiles.
-template <bool SYM, typename S>
+// Lim = ControlLimits (SYM = true, S = double only): the box form of the symmetric recursion for the per-rotor thrust limits
+// (qilqr_set_control_limits): box QP per knot (box_qp.h), the full value updates, status QILQR_STATUS_QP_FAILED.  Without it (an
+// empty pack) the kernel takes exactly the arguments it always took: the limits reach only the kernel of the extension.
+template <bool SYM, typename S, typename... Lim>
 __global__ __launch_bounds__(64) void k_backward(ModelConsts<double> c, SolveParams p, BatchState st,
-                                                 int B, int n, int force) {
+                                                 int B, int n, int force, Lim... lim) {
+  constexpr bool BOX = sizeof...(Lim) == 1;
+  static_assert(!BOX || (SYM && std::is_same<S, double>::value), "the box form is the symmetric fp64 recursion");
   const int b = blockIdx.x;
   if (b >= B) return;
   const int lane = threadIdx.x;
@@ -154,6 +175,9 @@ __global__ __launch_bounds__(64) void k_backward(ModelConsts<double> c, SolvePar
   double va[3] = {0.0, 0.0, 0.0};   // V_xx[j][4 kc + kk]  (A operand)
   double vxl[3] = {0.0, 0.0, 0.0};  // V_x[4 kc + kk]
   double QuTk = 0.0, kTQuuk = 0.0;
+  // box form: the controls of the current iterate (the centre of each knot's box), and whether a QP failed
+  const S *ucur = (const S *)st.traj[cur] + knot_base<true>(b, n, 18);
+  bool qp_failed = false;
 
   // software pipeline: the operands of knot i-1 are requested before the chain of knot i starts
   double m[3], cx[3], gcj;
@@ -197,6 +221,11 @@ __global__ __launch_bounds__(64) void k_backward(ModelConsts<double> c, SolvePar
     // on the load at the top of the loop; the next knot of the general kernel is of the other kind: C transposed behind a kind-2 knot)
     const S m_s0 = *op[0], m_s1 = *op[1], m_s2 = *op[2], g_s = *op[6];
     const S cx_s0 = (KIND == 2) ? *opt[0] : *op[3], cx_s1 = (KIND == 2) ? *opt[1] : *op[4], cx_s2 = (KIND == 2) ? *opt[2] : *op[5];
+    double ui[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (BOX) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a) ui[a] = (double)ucur[knot_elem<true>(i, 14 + a, 18)];  // (the same address in every lane: one broadcast load)
+    }
     QSTAMP(0);  // prefetch issue
     const d4 T = bw_tile_T(va, m);
     QKEEP(T[0]); QKEEP(T[3]);
@@ -274,7 +303,25 @@ __global__ __launch_bounds__(64) void k_backward(ModelConsts<double> c, SolvePar
     // one right-hand side per lane: K[:, j] = -Quu^-1 Q_xu[j, :]^T in lanes j < 12 and k = -Quu^-1 Q_u in lane 12
     // (ilqr.hh:127-128); k is then broadcast
     double kcol[4];
-    if constexpr (SYM) {
+    // box form: the QP's solution k (every lane solves the same QP on the same broadcast data) and its clamped set
+    double kbox[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (BOX) {
+      const ControlLimits &L = (lim, ...);
+      double lb[4], hb[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        lb[a] = L.lo[a] - ui[a];
+        hb[a] = L.hi[a] - ui[a];
+      }
+      unsigned clamped = 0;
+      BoxLdl f;
+      if (!box_qp(Quu, Qu, lb, hb, kbox, clamped, f)) qp_failed = true;
+      // lane j < 12: K[:, j] on the free rows from the masked factor, zero on the clamped rows; lanes 12..15: k (lane 12 stores it)
+      double kc[4];
+      box_gain_column(f, clamped, rhs, kc);
+#pragma unroll
+      for (int a = 0; a < 4; ++a) kcol[a] = (j < 12) ? kc[a] : kbox[a];
+    } else if constexpr (SYM) {
       // LDL^T of the lower triangle of Q_uu without pivoting (Q_uu = 2 R + J_u^T V_xx J_u is positive definite for the
       // weights this kernel is launched for; the reference's Eigen LDLT pivots on the diagonal: same result in exact arithmetic)
       const Ldlt4 f = ldlt4_factor(Quu);
@@ -302,9 +349,25 @@ __global__ __launch_bounds__(64) void k_backward(ModelConsts<double> c, SolvePar
     // expected cost reduction terms (ilqr.hh:136-140): in lane 12 the right-hand side is Q_u and the
     // solution is k, so Q_u^T k = rhs . kcol there; every lane accumulates its own column's value and
     // lane 12's sum is read after the loop
-    QuTk += rhs[0] * kcol[0] + rhs[1] * kcol[1] + rhs[2] * kcol[2] + rhs[3] * kcol[3];
     double vx;
-    if constexpr (SYM) {
+    if constexpr (BOX) {
+      // With a bound active the shortcuts of the symmetric form below do not hold; the full updates
+      //   V_x = Q_x + Q_xu k + K^T (Q_uu k + Q_u),  V_xx = Q_xx + Q_xu K,  Q_u^T k,  k^T Q_uu k
+      // (V_xx stays exact: K's clamped rows are zero and Q_uu,FF K_F = -Q_ux,F, so K^T Q_uu K + K^T Q_ux = 0).  Lane j holds Q_xu[j, :]
+      // (rhs) and K[:, j] (kcol); k, Q_uu, Q_u are the same in every lane, so are the two terms.
+      double qk[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        qk[a] = Quu[a * 4 + 0] * kbox[0] + Quu[a * 4 + 1] * kbox[1] + Quu[a * 4 + 2] * kbox[2] + Quu[a * 4 + 3] * kbox[3];
+      QuTk += Qu[0] * kbox[0] + Qu[1] * kbox[1] + Qu[2] * kbox[2] + Qu[3] * kbox[3];
+      kTQuuk += qk[0] * kbox[0] + qk[1] * kbox[1] + qk[2] * kbox[2] + qk[3] * kbox[3];
+      vx = ghat + (rhs[0] * kbox[0] + rhs[1] * kbox[1] + rhs[2] * kbox[2] + rhs[3] * kbox[3]) +
+           (kcol[0] * (qk[0] + Qu[0]) + kcol[1] * (qk[1] + Qu[1]) + kcol[2] * (qk[2] + Qu[2]) + kcol[3] * (qk[3] + Qu[3]));
+#pragma unroll
+      for (int kc = 0; kc < 3; ++kc) vxl[kc] = __shfl(vx, 4 * kc + kk);
+      H = __builtin_amdgcn_mfma_f64_16x16x4f64(H[3], sel4(kcol, kk), H, 0, 0, 0);
+    } else if constexpr (SYM) {
+      QuTk += rhs[0] * kcol[0] + rhs[1] * kcol[1] + rhs[2] * kcol[2] + rhs[3] * kcol[3];
       // With Q_uu symmetric and K = -Quu^-1 Q_ux, k = -Quu^-1 Q_u, the reference's updates
       //   V_x = Q_x - K^T Quu k,  V_xx = Q_xx - K^T Quu K,  k^T Quu k      (ilqr.hh:132-133, 139)
       // are, term by term,  Q_x + K^T Q_u,  Q_xx + Q_xu K,  -Q_u^T k  (they differ from the reference's
@@ -319,6 +382,7 @@ __global__ __launch_bounds__(64) void k_backward(ModelConsts<double> c, SolvePar
       for (int kc = 0; kc < 3; ++kc) vxl[kc] = __shfl(vx, 4 * kc + kk);  // V_x[r] lives in lanes with j == r
       H = __builtin_amdgcn_mfma_f64_16x16x4f64(H[3], sel4(kcol, kk), H, 0, 0, 0);
     } else {
+      QuTk += rhs[0] * kcol[0] + rhs[1] * kcol[1] + rhs[2] * kcol[2] + rhs[3] * kcol[3];
       // (K^T Quu)[j][:], then V_x = Q_x - (K^T Quu) k   (ilqr.hh:132)
       double mc[4], kff[4];
 #pragma unroll
@@ -357,7 +421,12 @@ __global__ __launch_bounds__(64) void k_backward(ModelConsts<double> c, SolvePar
     QKEEP(va[0]); QKEEP(vxl[2]);
     QSTAMP(7);  // V_xx MFMA, gain stores, hand-off
   };
-  if constexpr (SYM) {
+  if constexpr (BOX) {
+    for (int i = n - 1; i >= 0; --i) {
+      knot(i, std::integral_constant<int, 0>());
+      if (qp_failed) break;  // (uniform: every lane solved the same QP)
+    }
+  } else if constexpr (SYM) {
     for (int i = n - 1; i >= 0; --i) knot(i, std::integral_constant<int, 0>());
   } else {
     for (int i = n - 1; i >= 0; i -= 2) {
@@ -370,6 +439,16 @@ __global__ __launch_bounds__(64) void k_backward(ModelConsts<double> c, SolvePar
   if (lane == 0 && st.stamps)
     for (int k = 0; k < 8; ++k) st.stamps[(long)b * 8 + k] = stamp_sum[k];
 #endif
+  if constexpr (BOX) {
+    // (the two terms are the same in every lane)
+    if (lane == 0) {
+      st.terms[2 * b] = QuTk;
+      st.terms[2 * b + 1] = kTQuuk;
+      st.n_bwd[b] += 1;
+      if (!force) arm_line_search_box(p, st, b, st.iters[b], st.cost[b], QuTk, kTQuuk, qp_failed);
+    }
+    return;
+  }
   QuTk = bcast_lane(QuTk, 12);
   kTQuuk = SYM ? -QuTk : bcast_lane(kTQuuk, 12);
   if (lane == 0) {

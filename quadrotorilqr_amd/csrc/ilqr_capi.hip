@@ -67,6 +67,8 @@ struct qilqr_solver {
   void *d_consts = nullptr;     // the model constants in device memory (k_linearize reads them where it uses them)
   bool f32 = false;             // mixed-precision mode (qilqr_device_config.precision == 1)
   int integrator = 0;           // 0 explicit Euler (the reference), 1 the Runge-Kutta extension (qilqr_set_integrator)
+  bool limited = false;         // per-rotor thrust limits set (qilqr_set_control_limits): the box route
+  ControlLimits limits{};       // ... and their values
   ModelConsts<float> constsf;   // the model constants for the fp32 lane-local kernels
   // workspace
   long cap_B = 0, cap_n = 0;
@@ -457,14 +459,14 @@ int launch_linearize(qilqr_solver *s, long B, long n, int which, int need_flag, 
 // 16384: 593k / 512k, 65536: 654k / 587k); the one-wavefront kernel stays for force_general = 2.
 // k_backward2 (a matrix and a gradient wavefront per trajectory) was the choice below 512 trajectories in rounds 1 and 2; it
 // wins nowhere by more than 2 % and lives in the diagnostics build (force_general = 3 there).
-// The Runge-Kutta extension and non-symmetric weights take the one-wavefront kernel at every size.
+// The Runge-Kutta extension, the thrust limits and non-symmetric weights take the one-wavefront kernel at every size.
 #ifndef QILQR_GFAC_MIN_LIVE
 #define QILQR_GFAC_MIN_LIVE 3072
 #endif
 constexpr long GFAC_MIN_LIVE = QILQR_GFAC_MIN_LIVE;  // running trajectories from which the gradient wavefront factors Q_uu (launch_backward)
 enum BackwardKind { BW_FOUR, BW_TWO, BW_ONE, BW_FUSED };
 BackwardKind backward_kind(const qilqr_solver *s, long load_B) {
-  if (s->integrator == 1 || !s->symmetric) return BW_ONE;
+  if (s->integrator == 1 || !s->symmetric || s->limited) return BW_ONE;
 #ifdef QILQR_WITH_BACKWARD2
   if (s->dev.force_general == 3) return BW_TWO;
 #endif
@@ -536,6 +538,9 @@ int launch_backward(qilqr_solver *s, long B, long n, int force) {
       launch(s, K_BACKWARD, k_backward2<double>, dim3((unsigned)B), dim3(128), s->consts, s->params, s->st, (int)B,
              (int)n, force);
 #endif
+  } else if (s->limited) {  // the thrust-limit extension: the box form (symmetric weights, fp64: qilqr_set_control_limits)
+    launch(s, K_BACKWARD, (k_backward<true, double, ControlLimits>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, (int)B, (int)n,
+           force, s->limits);
   } else if (s->symmetric) {
     if (s->f32) QILQR_LAUNCH_BWD(true, float);
     else QILQR_LAUNCH_BWD(true, double);
@@ -562,7 +567,12 @@ int launch_rollout(qilqr_solver *s, long B, long n, int need_flag, long ordinal 
   //                (65536: 698k against 655k solves/s, 16384: 596k / 543k, profiles/r04_compaction.txt)
   const long load_B = std::max(B, s->total_B);
   const int choice = s->dev.single_wave_rollout;
-  if (s->integrator == 1) {  // the Runge-Kutta extension: the lane-per-trajectory kernel only
+  if (s->limited) {  // the thrust-limit extension (either integrator): the lane-per-trajectory kernel, controls clamped
+    if (s->integrator == 1)
+      launch(s, K_ROLLOUT, (k_rollout<double, 1, ControlLimits>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, s->limits);
+    else
+      launch(s, K_ROLLOUT, (k_rollout<double, 0, ControlLimits>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, s->limits);
+  } else if (s->integrator == 1) {  // the Runge-Kutta extension: the lane-per-trajectory kernel only
     launch(s, K_ROLLOUT, (k_rollout<double, 1>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag);
   } else if (choice == 1) {  // (a forced choice is honoured at every batch size; until round 4 also the choice above 16384)
     if (s->f32)
@@ -591,7 +601,7 @@ int launch_rollout(qilqr_solver *s, long B, long n, int need_flag, long ordinal 
 bool fuse_kinds(const qilqr_solver *s, long B, long total_B, bool tiled) {
   const bool off = s->dev.round_launch == 1;  // (qilqr_device_config.round_launch: three launches per round, A/B)
   const long load_B = std::max(B, total_B);
-  if (off || s->integrator != 0 || !s->symmetric || !tiled) return false;
+  if (off || s->integrator != 0 || s->limited || !s->symmetric || !tiled) return false;
   // (force_general = 8 with the combined launch: k_round with the six-wavefront backward pass in EVERY launch -- tests, A/B)
   if (!(s->dev.force_general == 0 || s->dev.force_general == 5 || s->dev.force_general == 8)) return false;
   if (s->dev.force_general != 8 && backward_kind(s, load_B) != BW_FUSED) return false;
@@ -726,7 +736,7 @@ struct TailFuse {
 #endif
 bool late_tail_kinds(const qilqr_solver *s, long B, long total_B, bool tiled, long *from) {
   const long load_B = std::max(B, total_B);
-  if (!QILQR_LATE_TAIL || s->dev.round_launch == 1 || s->integrator != 0 || !s->symmetric || !tiled) return false;
+  if (!QILQR_LATE_TAIL || s->dev.round_launch == 1 || s->integrator != 0 || s->limited || !s->symmetric || !tiled) return false;
   if (s->dev.force_general != 0 || load_B <= R16_MAX_B || backward_kind(s, load_B) != BW_FOUR) return false;
   if (s->dev.single_wave_rollout == 0) *from = ROLLOUT16_FROM;
   else if (s->dev.single_wave_rollout == 3) *from = 0;
@@ -1248,7 +1258,7 @@ int check_quaternions(const double *traj, long count, const char *what) {
 bool use_persistent(const qilqr_solver *s, long B) {
   (void)B;
 #ifdef QILQR_WITH_SOLVE4
-  return s->symmetric && s->dev.persistent == 1 && s->integrator == 0;
+  return s->symmetric && s->dev.persistent == 1 && s->integrator == 0 && !s->limited;
 #else
   (void)s;
   return false;  // k_solve4 is in the diagnostics build (qilqr_create refuses persistent = 1 here)
@@ -1281,6 +1291,8 @@ int solve_batch_device_impl(qilqr_solver *s, const double *d_init, const double 
                             double *d_out_traj, double *d_out_cost, int32_t *d_out_status, int32_t *d_out_iters,
                             int32_t *d_out_n_bwd, int32_t *d_out_n_fwd, bool drain) {
   if (!s || !d_init) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  if (s->limited && s->dev.persistent == 1)
+    return fail(QILQR_ERR_INVALID_ARG, "control limits: persistent = 1 (k_solve4) has no box form; take the rounds (persistent = 0)");
   const RoctxRange range(s, "batch solve, trajectories:", (long)B);
   int rc = begin_batch(s, B, n, d_desired_batch);
   if (rc) return rc;
@@ -1644,6 +1656,46 @@ int qilqr_set_integrator(qilqr_solver *s, int32_t integrator) {
   free_workspace(s);
   s->integrator = integrator;
   s->layout = make_layout(s->layout.sym != 0, s->layout.ur_zero != 0, integrator == 1);
+  return QILQR_OK;
+}
+
+int qilqr_set_control_limits(qilqr_solver *s, const double *lo, const double *hi) {
+  if (!s) return fail(QILQR_ERR_INVALID_ARG, "null solver");
+  if ((lo == nullptr) != (hi == nullptr)) return fail(QILQR_ERR_INVALID_ARG, "control limits: lo and hi are both given or both NULL");
+  if (lo) {
+    for (int a = 0; a < 4; ++a)
+      if (std::isnan(lo[a]) || std::isnan(hi[a]) || !(lo[a] < hi[a]))
+        return fail(QILQR_ERR_INVALID_ARG, "control limits: rotor " + std::to_string(a) + " needs lo < hi and no NaN");
+    if (s->f32) return fail(QILQR_ERR_INVALID_ARG, "control limits need precision 0 (fp64)");
+    if (!s->symmetric)
+      return fail(QILQR_ERR_INVALID_ARG, "control limits need exactly symmetric Q and R (and force_general != 1): the box form is the symmetric recursion");
+    // the QP needs a strictly convex Q_uu = 2 R + J_u^T V_xx J_u: R positive definite (Cholesky of 2 R)
+    double L[16] = {0};
+    bool pd = true;
+    for (int i = 0; i < 4 && pd; ++i)
+      for (int k = 0; k <= i && pd; ++k) {
+        double v = 2.0 * s->consts.R[i * 4 + k];
+        for (int m = 0; m < k; ++m) v -= L[i * 4 + m] * L[k * 4 + m];
+        if (i == k) {
+          pd = v > 0.0;
+          L[i * 4 + i] = pd ? std::sqrt(v) : 0.0;
+        } else {
+          L[i * 4 + k] = v / L[k * 4 + k];
+        }
+      }
+    if (!pd) return fail(QILQR_ERR_INVALID_ARG, "control limits need R positive definite (the box QP of every knot must be strictly convex)");
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  // (nothing of the workspace depends on the limits: the record placement is chosen per call, begin_batch -> records_tiled)
+  s->limited = lo != nullptr;
+  if (lo)
+    for (int a = 0; a < 4; ++a) {
+      s->limits.lo[a] = lo[a];
+      s->limits.hi[a] = hi[a];
+    }
+  else
+    s->limits = ControlLimits{};
   return QILQR_OK;
 }
 
@@ -2493,17 +2545,24 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
     t += "arithmetic: symmetric-weight forms (Q == Q^T and R == R^T exactly: unpivoted LDL^T, V_x = Q_x + K^T Q_u, V_xx = Q_xx + Q_xu K on a symmetric "
          "accumulator; force_general = 1 selects the reference's own forms)";
   t += s->integrator == 1 ? "; Runge-Kutta step (extension)" : "; explicit Euler step (the reference's)";
+  if (s->limited) {
+    char lim[256];
+    std::snprintf(lim, sizeof lim, "; control limits [lo, hi] (extension): lo = {%g, %g, %g, %g}, hi = {%g, %g, %g, %g} N, box QP per knot",
+                  s->limits.lo[0], s->limits.lo[1], s->limits.lo[2], s->limits.lo[3], s->limits.hi[0], s->limits.hi[1], s->limits.hi[2], s->limits.hi[3]);
+    t += lim;
+  }
   t += s->f32 ? "; mixed precision (fp32 storage and lane-local arithmetic, fp64 recursion and cost sums)" : "; fp64";
   t += "; backward: ";
   t += persistent ? "k_solve4 (one launch per solve)" : kind == BW_FUSED ? "k_backward4, fused matrix + gradient wavefronts" : kind == BW_FOUR ? "k_backward4, six wavefronts"
-       : kind == BW_TWO ? "k_backward2" : (s->symmetric ? "k_backward<true>, one wavefront per trajectory" : "k_backward<false>, one wavefront per trajectory (general kernel)");
+       : kind == BW_TWO ? "k_backward2" : s->limited ? "k_backward<true> box form, one wavefront per trajectory"
+       : (s->symmetric ? "k_backward<true>, one wavefront per trajectory" : "k_backward<false>, one wavefront per trajectory (general kernel)");
   if (kind == BW_FOUR || (kind == BW_FUSED && s->dev.force_general == 0 && load_B >= GFAC_MIN_LIVE))
     t += kind == BW_FOUR ? " (Q_uu factored by the gradient wavefront in launches with " + std::to_string(GFAC_MIN_LIVE) + " or more running trajectories, by the matrix wavefronts otherwise: the same bits)"
                          : " (six wavefronts, Q_uu factored by the gradient wavefront, while " + std::to_string(GFAC_MIN_LIVE) + " or more trajectories run: the same bits)";
   if (!persistent) {
     const int choice = s->dev.single_wave_rollout;
     t += "; rollout: ";
-    t += (s->integrator == 1 || choice == 1) ? "k_rollout" : (choice == 3 || (choice == 0 && load_B <= R16_MAX_B)) ? "k_rollout16"
+    t += (s->integrator == 1 || s->limited || choice == 1) ? "k_rollout" : (choice == 3 || (choice == 0 && load_B <= R16_MAX_B)) ? "k_rollout16"
          : choice == 0 ? "k_rollout3 for a trajectory's first " + std::to_string(ROLLOUT16_FROM) + " rollouts, k_rollout16 from there on" : "k_rollout3";
     // (nothing of the handle is touched: the launch helpers take the batch and the record placement the call WOULD have)
     const bool tiled = records_tiled(s, B, persistent);

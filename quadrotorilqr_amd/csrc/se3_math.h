@@ -1360,9 +1360,11 @@ QILQR_HD void control_law(const T *pt, const T *g, T alpha, const T dx[12], T u[
 
 // closed-loop rollout of one problem (ilqr.hh:149-172).  traj/gains/out point at this problem's
 // first element (knot_base) in the TILED or plain layout.
-template <bool TILED, typename T, int INTEG = 0>
+// LIM (the thrust-limit extension, qilqr_set_control_limits): u is clamped to [lo, hi] rotor by rotor after the control law; the
+// clamped control is what is stored, stepped with (and so linearised and costed).
+template <bool TILED, typename T, int INTEG = 0, bool LIM = false>
 QILQR_HD void rollout_problem(const ModelConsts<T> &c, const T *traj, const T *gains, T alpha,
-                              T *out, int n) {
+                              T *out, int n, const T *lo = nullptr, const T *hi = nullptr) {
   T pt[18], g[52];
   load_knot<TILED>(traj, 0, 18, pt);
   T t[3] = {pt[1], pt[2], pt[3]};
@@ -1383,6 +1385,10 @@ QILQR_HD void rollout_problem(const ModelConsts<T> &c, const T *traj, const T *g
     for (int a = 0; a < 6; ++a) dx[6 + a] = v[a] - pt[8 + a];
     T u[4];
     control_law(pt, g, alpha, dx, u);
+    if (LIM) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a) u[a] = u[a] < lo[a] ? lo[a] : (u[a] > hi[a] ? hi[a] : u[a]);
+    }
     const T o[18] = {pt[0], t[0], t[1], t[2], q[3], q[0], q[1], q[2], v[0], v[1], v[2], v[3], v[4], v[5],
                      u[0], u[1], u[2], u[3]};
 #pragma unroll

@@ -304,6 +304,21 @@ int qilqr_set_integrator(qilqr_solver *s, int32_t integrator);
  * lo = hi = NULL clears the limits: every result is then again the handle's without them.  Waits for the handle's stream. */
 int qilqr_set_control_limits(qilqr_solver *s, const double *lo, const double *hi);
 
+/* Per-problem models -- an EXTENSION: from this call on, problem b of every computing entry point of the handle (qilqr_solve_batch,
+ * qilqr_solve_batch_device, qilqr_backwards_pass, qilqr_forward_sim, qilqr_line_search) is solved with models[b] -- its own mass, g,
+ * inertia, arm length and torque ratio -- for a fleet of airframes, payloads of different mass, or one start under sampled models.
+ * dt, Q, R, the desired trajectory, the options, the integrator, restarts and thrust limits stay the handle's.  qilqr_cost_trajectory
+ * does not depend on the model (and takes any B).  The call copies the models into one record per problem (mass, g, inertia, its
+ * inverse, moment arms, the constant rows of J_u: quadrotorilqr_amd/csrc/batch_models.h), uploads them once, and waits for the
+ * handle's stream.  Runs on the general kernels -- the one-wavefront backward pass, the lane-per-trajectory rollout, k_linearize
+ * reading each problem's record -- with either integrator, with restarts, with thrust limits and with any weights they take; the
+ * compaction of the running trajectories is off.
+ * QILQR_ERR_BAD_INERTIA for a model qilqr_create would refuse ("Inertia matrix is not positive definite! (batch models: problem k)",
+ * k the first such index); QILQR_ERR_INVALID_ARG for a mixed-precision handle (precision = 1), and, while models are set, for a
+ * computing call whose B is not this B, a solve with persistent = 1, and qilqr_solve (one problem, the handle's model by definition).
+ * models = NULL with B = 0 clears them: every result is then again the handle's without them. */
+int qilqr_set_batch_models(qilqr_solver *s, const qilqr_model *models, int32_t B);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -384,6 +399,11 @@ int qilqr_solve_batch_sharded(qilqr_sharded *h, const double *init, const double
 #define QILQR_TRANSPORT_RCCL 1
 #define QILQR_TRANSPORT_PEER_COPY 2
 int qilqr_sharded_set_transport(qilqr_sharded *h, int32_t transport);
+
+/* qilqr_set_batch_models for a sharded handle: shard r's solver gets models[begin .. begin + count) (qilqr_shard_range of B), and the
+ * sharded solves (qilqr_solve_batch_sharded, qilqr_solve_batch_sharded_device) refuse another B.  The models are checked for the whole
+ * batch first (the index in an error is the batch's); a failure leaves every shard without models.  NULL, 0 clears them. */
+int qilqr_sharded_set_batch_models(qilqr_sharded *h, const qilqr_model *models, int32_t B);
 const char *qilqr_sharded_transport(qilqr_sharded *h);
 int qilqr_solve_batch_sharded_device(qilqr_sharded *h, const double *init, const double *desired_batch, int32_t B, int32_t n,
                                      int32_t root, double *d_out_traj, double *d_out_cost, int32_t *d_out_status,
@@ -413,7 +433,8 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
 
 /* ABI version of this header: 7 (qilqr_device_config grew by round_launch, rounds_per_launch, fuse_in_flight, dense_weights -- the
  * switches that were environment variables -- and the *_sized entry points carry the caller's structure size; version 6 added
- * `compaction`).  qilqr_set_control_limits and QILQR_STATUS_QP_FAILED were added within version 7: no structure changed. */
+ * `compaction`).  qilqr_set_control_limits, QILQR_STATUS_QP_FAILED, qilqr_set_batch_models and qilqr_sharded_set_batch_models were added
+ * within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

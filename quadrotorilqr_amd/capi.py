@@ -38,7 +38,7 @@ EXPORTS = (
     "qilqr_create", "qilqr_create_sized", "qilqr_destroy", "qilqr_last_error", "qilqr_solve", "qilqr_solve_batch",
     "qilqr_solve_batch_device", "qilqr_cost_trajectory", "qilqr_backwards_pass", "qilqr_forward_sim",
     "qilqr_line_search", "qilqr_cost_history", "qilqr_profile_reset", "qilqr_profile_get", "qilqr_profile_mode", "qilqr_set_regularisation",
-    "qilqr_set_integrator", "qilqr_set_control_limits",
+    "qilqr_set_integrator", "qilqr_set_control_limits", "qilqr_set_batch_models", "qilqr_sharded_set_batch_models",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -100,6 +100,8 @@ def load():
         lib.qilqr_sharded_transport.argtypes = [C.c_void_p]
         lib.qilqr_sharded_transport.restype = C.c_char_p
         lib.qilqr_set_control_limits.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        lib.qilqr_set_batch_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.qilqr_sharded_set_batch_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         _lib = lib
     return _lib
 
@@ -162,6 +164,50 @@ def _create_args(self, mass_kg, inertia, arm_length_m, torque_to_thrust_ratio_m,
                       int(single_wave_rollout), {"f64": 0, "f32": 1}[precision], int(streams), int(persistent), int(compaction),
                       int(round_launch), int(rounds_per_launch), int(fuse_in_flight), int(dense_weights))
     return m, Q, R, o, dc
+
+
+MODEL_FIELDS = ("mass_kg", "inertia", "arm_length_m", "torque_to_thrust_ratio_m", "g_mpss")
+
+
+def model_array(models):
+    """qilqr_model[B] for qilqr_set_batch_models: a sequence of dicts shaped like problems.MODEL_D, or a dict of arrays mass_kg[B],
+    inertia[B, 3, 3], arm_length_m[B], torque_to_thrust_ratio_m[B], g_mpss[B] (scalars, and one 3x3 inertia, broadcast)."""
+    if isinstance(models, dict):
+        cols = {k: np.asarray(models[k], dtype=np.float64) for k in MODEL_FIELDS}
+        if cols["inertia"].shape[-2:] != (3, 3):
+            raise TypeError("inertia must be 3x3 or [B, 3, 3]")
+        lead = [cols[k].shape for k in MODEL_FIELDS if k != "inertia"] + [cols["inertia"].shape[:-2]]
+        try:
+            shape = np.broadcast_shapes(*lead)
+        except ValueError as e:
+            raise TypeError(f"model arrays do not broadcast to one batch: {lead}") from e
+        if len(shape) != 1:
+            raise TypeError("the model arrays must be one-dimensional over the batch (a scalar broadcasts)")
+        B = shape[0]
+        cols = {k: np.broadcast_to(v, (B, 3, 3) if k == "inertia" else (B,)) for k, v in cols.items()}
+    else:
+        models = list(models)
+        B = len(models)
+        cols = {k: np.array([m[k] for m in models], dtype=np.float64).reshape((B, 3, 3) if k == "inertia" else (B,)) for k in MODEL_FIELDS}
+    if B == 0:
+        raise TypeError("no models: clear_models() switches the per-problem models off")
+    arr = (Model * B)()
+    for b in range(B):
+        m = arr[b]
+        m.mass_kg = cols["mass_kg"][b]
+        for i, v in enumerate(cols["inertia"][b].reshape(9)):
+            m.inertia[i] = v
+        m.arm_length_m = cols["arm_length_m"][b]
+        m.torque_to_thrust_ratio_m = cols["torque_to_thrust_ratio_m"][b]
+        m.g_mpss = cols["g_mpss"][b]
+    return arr
+
+
+def _raise_models(rc):
+    """_raise, with the index of the first bad model kept in the message (the reference's text, then the problem)"""
+    if rc == ERR_BAD_INERTIA:
+        raise RuntimeError(load().qilqr_last_error().decode())
+    _raise(rc)
 
 
 def _batch_outputs(init, out):
@@ -398,6 +444,20 @@ class QuadrotorILQRBatch:
         if rc:
             _raise(rc)
 
+    def set_models(self, models):
+        """Per-problem models (an extension): problem b of every batch entry point is solved with models[b] -- see model_array for the
+        forms `models` takes, and qilqr_set_batch_models in include/quadrotor_ilqr.h.  Every call is then over exactly that many
+        problems.  clear_models() switches it off again."""
+        arr = model_array(models)
+        rc = load().qilqr_set_batch_models(self._h, C.cast(arr, C.c_void_p), C.c_int32(len(arr)))
+        if rc:
+            _raise_models(rc)
+
+    def clear_models(self):
+        rc = load().qilqr_set_batch_models(self._h, None, C.c_int32(0))
+        if rc:
+            _raise(rc)
+
     def profile_get(self):
         p = Profile()
         rc = load().qilqr_profile_get(self._h, C.byref(p))
@@ -469,6 +529,18 @@ class QuadrotorILQRSharded:
             rc = load().qilqr_set_control_limits(load().qilqr_sharded_solver(self._h, C.c_int32(r)), _p(lo), _p(hi))
             if rc:
                 _raise(rc)
+
+    def set_models(self, models):
+        """QuadrotorILQRBatch.set_models for the sharded batch: each shard's solver gets its slice (qilqr_sharded_set_batch_models)"""
+        arr = model_array(models)
+        rc = load().qilqr_sharded_set_batch_models(self._h, C.cast(arr, C.c_void_p), C.c_int32(len(arr)))
+        if rc:
+            _raise_models(rc)
+
+    def clear_models(self):
+        rc = load().qilqr_sharded_set_batch_models(self._h, None, C.c_int32(0))
+        if rc:
+            _raise(rc)
 
     def clear_control_limits(self):
         for r in range(len(self.devices)):

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "batch_models.h"
 #include "se3_math.h"
 
 namespace qilqr {
@@ -74,6 +75,21 @@ inline bool make_model_consts(double mass, const double inertia[9], double arm, 
   std::memcpy(c->Q, Q, sizeof(c->Q));
   std::memcpy(c->R, R, sizeof(c->R));
   return true;
+}
+
+// The per-problem records of qilqr_set_batch_models (batch_models.h): make_model_consts of every model with the handle's dt, Q and R --
+// the same arithmetic, so each record holds the bits a handle created with that model has -- packed PM_WORDS doubles apart into tab.
+// M: a structure with the fields of qilqr_model.  Returns -1, or the index of the first model make_model_consts refuses (tab is then
+// partly written).
+template <typename M>
+inline long make_model_table(const M *models, long B, const double *Q, const double *R, double dt, double *tab) {
+  for (long b = 0; b < B; ++b) {
+    ModelConsts<double> c;
+    const M &m = models[b];
+    if (!make_model_consts(m.mass_kg, m.inertia, m.arm_length_m, m.torque_to_thrust_ratio_m, m.g_mpss, Q, R, dt, &c)) return b;
+    pack_problem_model(c, tab + b * PM_WORDS);
+  }
+  return -1;
 }
 
 }  // namespace qilqr

@@ -69,6 +69,9 @@ struct qilqr_solver {
   int integrator = 0;           // 0 explicit Euler (the reference), 1 the Runge-Kutta extension (qilqr_set_integrator)
   bool limited = false;         // per-rotor thrust limits set (qilqr_set_control_limits): the box route
   ControlLimits limits{};       // ... and their values
+  bool modeled = false;         // per-problem models set (qilqr_set_batch_models): the general route, every call of exactly models_B problems
+  long models_B = 0;            // ... for how many problems
+  double *d_models = nullptr;   // ... their records in device memory, [models_B][PM_WORDS] (batch_models.h)
   ModelConsts<float> constsf;   // the model constants for the fp32 lane-local kernels
   // workspace
   long cap_B = 0, cap_n = 0;
@@ -345,12 +348,21 @@ int from_tiled(qilqr_solver *s, double *d_plain, void *t0, void *t1, const int *
 // the buffer selectors
 bool use_persistent(const qilqr_solver *s, long B);
 bool records_tiled(const qilqr_solver *s, long load_B, bool persistent);
+// per-problem models (qilqr_set_batch_models): problem b reads record b, so every computing call is over the rows they were set for
+int check_batch_models(const qilqr_solver *s, long B) {
+  if (s->modeled && B != s->models_B)
+    return fail(QILQR_ERR_INVALID_ARG, "batch models were set for B = " + std::to_string(s->models_B) + " problems; this call has B = " +
+                                           std::to_string(B) + " (set them again, or clear them, for another batch)");
+  return QILQR_OK;
+}
 int begin_batch(qilqr_solver *s, long B, long n, const double *d_desired_batch) {
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
   if (!d_desired_batch && n > s->n_desired)
     return fail(QILQR_ERR_LENGTH_MISMATCH, "trajectory longer than desired trajectory");
+  int rc = check_batch_models(s, B);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(s->device));
-  int rc = ensure_workspace(s, B, n);
+  rc = ensure_workspace(s, B, n);
   if (rc) return rc;
   if (d_desired_batch) {
     if (!s->desired_tiled && (rc = dalloc_s(s, &s->desired_tiled, (size_t)tiled_count(s->cap_B, s->cap_n, 18)))) return rc;
@@ -409,6 +421,24 @@ int launch_linearize(qilqr_solver *s, long B, long n, int which, int need_flag, 
   launch(s, K_LINEARIZE, (k_linearize<S, LK, 0, TILED>), grid, dim3(QILQR_LIN_BLOCK), CONSTS, DCONSTS, s->st, (int)B, (int)n, which, need_flag, round)
 #define QILQR_LAUNCH_LIN_RK4(LK) \
   launch(s, K_LINEARIZE, (k_linearize<double, LK, 1, false>), grid, dim3(QILQR_LIN_BLOCK), s->consts, (const ModelConsts<double> *)s->d_consts, s->st, (int)B, (int)n, which, need_flag, round)
+  if (s->modeled) {  // the per-problem models extension: fp64, plain placement (the one-wavefront backward kernel reads the records)
+    const BatchModels bm{s->d_models};
+#define QILQR_LAUNCH_LIN_MOD(LK, INTEG)                                                                                                     \
+  launch(s, K_LINEARIZE, (k_linearize<double, LK, INTEG, false, BatchModels>), grid, dim3(QILQR_LIN_BLOCK), s->consts,                   \
+         (const ModelConsts<double> *)s->d_consts, s->st, (int)B, (int)n, which, need_flag, round, bm)
+    const int lk = (s->integrator == 0 && layout_kind(s->layout) == 2 && s->q_diag) ? 3 : layout_kind(s->layout);
+    switch (lk + (s->integrator == 1 ? 4 : 0)) {
+      case 0: QILQR_LAUNCH_LIN_MOD(0, 0); break;
+      case 1: QILQR_LAUNCH_LIN_MOD(1, 0); break;
+      case 2: QILQR_LAUNCH_LIN_MOD(2, 0); break;
+      case 3: QILQR_LAUNCH_LIN_MOD(3, 0); break;
+      case 4: QILQR_LAUNCH_LIN_MOD(0, 1); break;
+      case 5: QILQR_LAUNCH_LIN_MOD(1, 1); break;
+      default: QILQR_LAUNCH_LIN_MOD(2, 1); break;
+    }
+#undef QILQR_LAUNCH_LIN_MOD
+    return QILQR_OK;
+  }
   if (s->integrator == 1) {  // the Runge-Kutta extension: dense M at the head of the record, fp64 only, plain placement
     switch (layout_kind(s->layout)) {
       case 0: QILQR_LAUNCH_LIN_RK4(0); break;
@@ -459,14 +489,14 @@ int launch_linearize(qilqr_solver *s, long B, long n, int which, int need_flag, 
 // 16384: 593k / 512k, 65536: 654k / 587k); the one-wavefront kernel stays for force_general = 2.
 // k_backward2 (a matrix and a gradient wavefront per trajectory) was the choice below 512 trajectories in rounds 1 and 2; it
 // wins nowhere by more than 2 % and lives in the diagnostics build (force_general = 3 there).
-// The Runge-Kutta extension, the thrust limits and non-symmetric weights take the one-wavefront kernel at every size.
+// The Runge-Kutta extension, the thrust limits, the per-problem models and non-symmetric weights take the one-wavefront kernel at every size.
 #ifndef QILQR_GFAC_MIN_LIVE
 #define QILQR_GFAC_MIN_LIVE 3072
 #endif
 constexpr long GFAC_MIN_LIVE = QILQR_GFAC_MIN_LIVE;  // running trajectories from which the gradient wavefront factors Q_uu (launch_backward)
 enum BackwardKind { BW_FOUR, BW_TWO, BW_ONE, BW_FUSED };
 BackwardKind backward_kind(const qilqr_solver *s, long load_B) {
-  if (s->integrator == 1 || !s->symmetric || s->limited) return BW_ONE;
+  if (s->integrator == 1 || !s->symmetric || s->limited || s->modeled) return BW_ONE;
 #ifdef QILQR_WITH_BACKWARD2
   if (s->dev.force_general == 3) return BW_TWO;
 #endif
@@ -538,6 +568,15 @@ int launch_backward(qilqr_solver *s, long B, long n, int force) {
       launch(s, K_BACKWARD, k_backward2<double>, dim3((unsigned)B), dim3(128), s->consts, s->params, s->st, (int)B,
              (int)n, force);
 #endif
+  } else if (s->modeled) {  // the per-problem models extension (fp64): the constant rows of J_u from each problem's record
+    const BatchModels bm{s->d_models};
+    if (s->limited)  // ... with the thrust limits: the box form
+      launch(s, K_BACKWARD, (k_backward_models<true, ControlLimits>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, (int)B,
+             (int)n, force, bm, s->limits);
+    else if (s->symmetric)
+      launch(s, K_BACKWARD, (k_backward_models<true>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, (int)B, (int)n, force, bm);
+    else
+      launch(s, K_BACKWARD, (k_backward_models<false>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, (int)B, (int)n, force, bm);
   } else if (s->limited) {  // the thrust-limit extension: the box form (symmetric weights, fp64: qilqr_set_control_limits)
     launch(s, K_BACKWARD, (k_backward<true, double, ControlLimits>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, (int)B, (int)n,
            force, s->limits);
@@ -567,7 +606,17 @@ int launch_rollout(qilqr_solver *s, long B, long n, int need_flag, long ordinal 
   //                (65536: 698k against 655k solves/s, 16384: 596k / 543k, profiles/r04_compaction.txt)
   const long load_B = std::max(B, s->total_B);
   const int choice = s->dev.single_wave_rollout;
-  if (s->limited) {  // the thrust-limit extension (either integrator): the lane-per-trajectory kernel, controls clamped
+  if (s->modeled) {  // the per-problem models extension (either integrator, with or without limits): the lane-per-trajectory kernel
+    const BatchModels bm{s->d_models};
+    if (s->limited && s->integrator == 1)
+      launch(s, K_ROLLOUT, (k_rollout<double, 1, ControlLimits, BatchModels>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, s->limits, bm);
+    else if (s->limited)
+      launch(s, K_ROLLOUT, (k_rollout<double, 0, ControlLimits, BatchModels>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, s->limits, bm);
+    else if (s->integrator == 1)
+      launch(s, K_ROLLOUT, (k_rollout<double, 1, BatchModels>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, bm);
+    else
+      launch(s, K_ROLLOUT, (k_rollout<double, 0, BatchModels>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, bm);
+  } else if (s->limited) {  // the thrust-limit extension (either integrator): the lane-per-trajectory kernel, controls clamped
     if (s->integrator == 1)
       launch(s, K_ROLLOUT, (k_rollout<double, 1, ControlLimits>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, s->limits);
     else
@@ -601,7 +650,7 @@ int launch_rollout(qilqr_solver *s, long B, long n, int need_flag, long ordinal 
 bool fuse_kinds(const qilqr_solver *s, long B, long total_B, bool tiled) {
   const bool off = s->dev.round_launch == 1;  // (qilqr_device_config.round_launch: three launches per round, A/B)
   const long load_B = std::max(B, total_B);
-  if (off || s->integrator != 0 || s->limited || !s->symmetric || !tiled) return false;
+  if (off || s->integrator != 0 || s->limited || s->modeled || !s->symmetric || !tiled) return false;
   // (force_general = 8 with the combined launch: k_round with the six-wavefront backward pass in EVERY launch -- tests, A/B)
   if (!(s->dev.force_general == 0 || s->dev.force_general == 5 || s->dev.force_general == 8)) return false;
   if (s->dev.force_general != 8 && backward_kind(s, load_B) != BW_FUSED) return false;
@@ -736,7 +785,7 @@ struct TailFuse {
 #endif
 bool late_tail_kinds(const qilqr_solver *s, long B, long total_B, bool tiled, long *from) {
   const long load_B = std::max(B, total_B);
-  if (!QILQR_LATE_TAIL || s->dev.round_launch == 1 || s->integrator != 0 || s->limited || !s->symmetric || !tiled) return false;
+  if (!QILQR_LATE_TAIL || s->dev.round_launch == 1 || s->integrator != 0 || s->limited || s->modeled || !s->symmetric || !tiled) return false;
   if (s->dev.force_general != 0 || load_B <= R16_MAX_B || backward_kind(s, load_B) != BW_FOUR) return false;
   if (s->dev.single_wave_rollout == 0) *from = ROLLOUT16_FROM;
   else if (s->dev.single_wave_rollout == 3) *from = 0;
@@ -1258,7 +1307,7 @@ int check_quaternions(const double *traj, long count, const char *what) {
 bool use_persistent(const qilqr_solver *s, long B) {
   (void)B;
 #ifdef QILQR_WITH_SOLVE4
-  return s->symmetric && s->dev.persistent == 1 && s->integrator == 0 && !s->limited;
+  return s->symmetric && s->dev.persistent == 1 && s->integrator == 0 && !s->limited && !s->modeled;
 #else
   (void)s;
   return false;  // k_solve4 is in the diagnostics build (qilqr_create refuses persistent = 1 here)
@@ -1293,6 +1342,8 @@ int solve_batch_device_impl(qilqr_solver *s, const double *d_init, const double 
   if (!s || !d_init) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   if (s->limited && s->dev.persistent == 1)
     return fail(QILQR_ERR_INVALID_ARG, "control limits: persistent = 1 (k_solve4) has no box form; take the rounds (persistent = 0)");
+  if (s->modeled && s->dev.persistent == 1)
+    return fail(QILQR_ERR_INVALID_ARG, "batch models: persistent = 1 (k_solve4) has one model for the batch; take the rounds (persistent = 0)");
   const RoctxRange range(s, "batch solve, trajectories:", (long)B);
   int rc = begin_batch(s, B, n, d_desired_batch);
   if (rc) return rc;
@@ -1300,8 +1351,8 @@ int solve_batch_device_impl(qilqr_solver *s, const double *d_init, const double 
   if ((rc = to_tiled(s, d_init, s->st.traj[0], B, n, 18, persistent ? s->st.counters : nullptr))) return rc;
   const int nparts = (s->dev.sync_every > 1) ? auto_parts(s, B) : 1;
   // compaction: free-running rounds only (the host never waits for a plan), not beside the copy-back under the tail (it gathers by
-  // slot), the per-iteration cost history (rows by slot) or per-problem desired trajectories (they would have to move along)
-  s->compact = s->dev.compaction >= 0 && s->dev.sync_every > 1 && !persistent && !s->st.cost_hist && !s->st.desired_tiled && !s->early_out &&
+  // slot), the per-iteration cost history (rows by slot), per-problem desired trajectories or per-problem models (they would have to move along)
+  s->compact = s->dev.compaction >= 0 && s->dev.sync_every > 1 && !persistent && !s->st.cost_hist && !s->st.desired_tiled && !s->early_out && !s->modeled &&
                0.0 < s->params.max_iters &&
                (s->dev.compaction == 1 || (!fuse_backward_rollout(s, B) && backward_kind(s, B) != BW_ONE && s->st.layout.tiled));
   s->compact_out = CompactOut{d_out_traj, d_out_cost, d_out_status, d_out_iters, d_out_n_bwd, d_out_n_fwd};
@@ -1362,6 +1413,8 @@ int solve_batch_staged(qilqr_solver *s, const double *init, const double *desire
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
   if (!desired_batch && n > s->n_desired)
     return fail(QILQR_ERR_LENGTH_MISMATCH, "trajectory longer than desired trajectory");
+  int rc;
+  if ((rc = check_batch_models(s, B))) return rc;  // (before anything is enqueued)
   HIP_TRY(hipSetDevice(s->device));
   const size_t cnt = 18 * (size_t)B * n, tb = sizeof(double) * cnt;
   auto grow = [&](auto **p, size_t *cap, size_t want, size_t elem) -> hipError_t {
@@ -1390,7 +1443,6 @@ int solve_batch_staged(qilqr_solver *s, const double *init, const double *desire
   if (e == hipSuccess) e = hipMemcpyAsync(s->stage_traj, init, tb, hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess && desired_batch) e = hipMemcpyAsync(s->stage_des, desired_batch, tb, hipMemcpyHostToDevice, s->stream);
   if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("staging: ") + hipGetErrorString(e));
-  int rc;
   if ((rc = check_quaternions(init, (long)B * n, "initial trajectory")) ||
       (desired_batch && (rc = check_quaternions(desired_batch, (long)B * n, "desired trajectory")))) {
     (void)hipStreamSynchronize(s->stream);  // the uploads read the caller's buffers: finished before the error returns
@@ -1569,6 +1621,7 @@ void qilqr_destroy(qilqr_solver *s) {
   if (s->stage_int) (void)hipFree(s->stage_int);
   if (s->d_desired) (void)hipFree(s->d_desired);
   if (s->d_ctab) (void)hipFree(s->d_ctab);
+  if (s->d_models) (void)hipFree(s->d_models);
   if (s->d_consts) (void)hipFree(s->d_consts);
   if (s->h_counters) (void)hipHostFree(s->h_counters);
   if (s->h_active) (void)hipHostFree(s->h_active);
@@ -1696,6 +1749,35 @@ int qilqr_set_control_limits(qilqr_solver *s, const double *lo, const double *hi
     }
   else
     s->limits = ControlLimits{};
+  return QILQR_OK;
+}
+
+int qilqr_set_batch_models(qilqr_solver *s, const qilqr_model *models, int32_t B) {
+  if (!s) return fail(QILQR_ERR_INVALID_ARG, "null solver");
+  if (B < 0 || (models == nullptr) != (B == 0))
+    return fail(QILQR_ERR_INVALID_ARG, "batch models: B > 0 models, or models = NULL and B = 0 to clear them");
+  std::vector<double> tab;
+  if (models) {
+    if (s->f32) return fail(QILQR_ERR_INVALID_ARG, "batch models need precision 0 (fp64): the mixed-precision kernels have one model");
+    // every model gets qilqr_create's checks (make_model_consts), with the handle's dt, Q and R: the records hold the bits of such a handle
+    tab.resize((size_t)B * PM_WORDS);
+    const long bad = make_model_table(models, (long)B, s->consts.Q, s->consts.R, s->consts.dt, tab.data());
+    if (bad >= 0)
+      return fail(QILQR_ERR_BAD_INERTIA, "Inertia matrix is not positive definite! (batch models: problem " + std::to_string(bad) + ")");
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  // (nothing of the workspace depends on the models: the record placement is chosen per call, begin_batch -> records_tiled)
+  s->modeled = false;
+  s->models_B = 0;
+  if (s->d_models) (void)hipFree(s->d_models);
+  s->d_models = nullptr;
+  if (models) {
+    HIP_TRY(hipMalloc((void **)&s->d_models, sizeof(double) * tab.size()));
+    HIP_TRY(hipMemcpy(s->d_models, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    s->modeled = true;
+    s->models_B = B;
+  }
   return QILQR_OK;
 }
 
@@ -1850,6 +1932,9 @@ int qilqr_solve(qilqr_solver *s, const double *init, int32_t n, double *out_traj
                 int32_t debug_cap, int32_t *n_debug) {
   if (!s || !init || !out_traj) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   if (n <= 0) return fail(QILQR_ERR_INVALID_ARG, "empty trajectory");
+  if (s->modeled)
+    return fail(QILQR_ERR_INVALID_ARG, "batch models are set: qilqr_solve solves one problem with the handle's model; use qilqr_solve_batch, or "
+                                       "clear the models");
   int rc;
   if ((rc = check_quaternions(init, n, "initial trajectory"))) return rc;
   if ((rc = begin_batch(s, 1, n, nullptr))) return rc;
@@ -1921,6 +2006,13 @@ int qilqr_solve(qilqr_solver *s, const double *init, int32_t n, double *out_traj
 
 int qilqr_cost_trajectory(qilqr_solver *s, const double *traj, int32_t B, int32_t n, double *cost) {
   if (!s || !traj || !cost) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  // the cost does not depend on the model: with per-problem models set, this call (of any B) takes the handle's own route
+  struct ModelsOff {
+    qilqr_solver *s;
+    bool was;
+    ~ModelsOff() { s->modeled = was; }
+  } models_off{s, s->modeled};
+  s->modeled = false;
   int rc = begin_batch(s, B, n, nullptr);
   if (rc) return rc;
   if ((rc = upload_tiled(s, traj, s->st.traj[0], B, n, 18))) return rc;
@@ -2107,6 +2199,7 @@ struct qilqr_sharded {
   std::vector<hipEvent_t> done;          // per shard: its solve (and gather kernel) have finished
   std::mutex gather_mutex;               // the shards' host threads enqueue their transfers one at a time (shared communicators / streams)
   std::string info;
+  int32_t models_B = -1;                 // per-problem models set for this many problems (qilqr_sharded_set_batch_models), -1: none
 };
 
 extern "C++" {
@@ -2347,6 +2440,8 @@ int qilqr_solve_batch_sharded(qilqr_sharded *h, const double *init, const double
                               int32_t *out_n_bwd, int32_t *out_n_fwd) {
   if (!h || h->solvers.empty() || !init) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
+  if (h->models_B >= 0 && B != h->models_B)  // (a shard with no rows of the models' batch has none set: checked here, for the whole batch)
+    return fail(QILQR_ERR_INVALID_ARG, "batch models were set for B = " + std::to_string(h->models_B) + " problems; this call has B = " + std::to_string(B));
   DeviceGuard guard;
   try {
     const ShardCall c{init, desired_batch, B, n, out_traj, out_cost, out_status, out_iters, out_n_bwd, out_n_fwd, true};
@@ -2354,6 +2449,35 @@ int qilqr_solve_batch_sharded(qilqr_sharded *h, const double *init, const double
   } catch (...) {
     return fail(QILQR_ERR_INVALID_ARG, "qilqr_solve_batch_sharded: out of host memory");
   }
+}
+
+int qilqr_sharded_set_batch_models(qilqr_sharded *h, const qilqr_model *models, int32_t B) {
+  if (!h || h->solvers.empty()) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  if (B < 0 || (models == nullptr) != (B == 0))
+    return fail(QILQR_ERR_INVALID_ARG, "batch models: B > 0 models, or models = NULL and B = 0 to clear them");
+  const int32_t k = (int32_t)h->solvers.size();
+  if (models) {  // checked for the whole batch first, so that an error names the batch's index (every shard has the same dt, Q and R)
+    const qilqr_solver *s0 = h->solvers[0];
+    if (s0->f32) return fail(QILQR_ERR_INVALID_ARG, "batch models need precision 0 (fp64): the mixed-precision kernels have one model");
+    std::vector<double> tab((size_t)B * PM_WORDS);
+    const long bad = make_model_table(models, (long)B, s0->consts.Q, s0->consts.R, s0->consts.dt, tab.data());
+    if (bad >= 0)
+      return fail(QILQR_ERR_BAD_INERTIA, "Inertia matrix is not positive definite! (batch models: problem " + std::to_string(bad) + ")");
+  }
+  DeviceGuard guard;
+  h->models_B = -1;
+  for (int32_t r = 0; r < k; ++r) {
+    int32_t b0 = 0, cnt = 0;
+    (void)qilqr_shard_range(B, k, r, &b0, &cnt);
+    const int rc = qilqr_set_batch_models(h->solvers[r], cnt ? models + b0 : nullptr, cnt);
+    if (rc) {  // (none half set: every shard cleared)
+      const std::string msg = g_last_error;
+      for (int32_t q = 0; q < k; ++q) (void)qilqr_set_batch_models(h->solvers[q], nullptr, 0);
+      return fail(rc, msg);
+    }
+  }
+  if (models) h->models_B = B;
+  return QILQR_OK;
 }
 
 int qilqr_sharded_set_transport(qilqr_sharded *h, int32_t transport) {
@@ -2473,6 +2597,8 @@ int qilqr_solve_batch_sharded_device(qilqr_sharded *h, const double *init, const
                                      int32_t *d_out_iters, int32_t *d_out_n_bwd, int32_t *d_out_n_fwd, double *gather_ms) {
   if (!h || h->solvers.empty() || !init) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
+  if (h->models_B >= 0 && B != h->models_B)
+    return fail(QILQR_ERR_INVALID_ARG, "batch models were set for B = " + std::to_string(h->models_B) + " problems; this call has B = " + std::to_string(B));
   const int32_t k = (int32_t)h->solvers.size();
   if (root < 0 || root >= k) return fail(QILQR_ERR_INVALID_ARG, "root must be a shard index");
   DeviceGuard guard;
@@ -2551,10 +2677,15 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
                   s->limits.lo[0], s->limits.lo[1], s->limits.lo[2], s->limits.lo[3], s->limits.hi[0], s->limits.hi[1], s->limits.hi[2], s->limits.hi[3]);
     t += lim;
   }
+  if (s->modeled)
+    t += "; per-problem models (extension): " + std::to_string(s->models_B) + " problems, each with its own mass, g, inertia and moment arms" +
+         (B != s->models_B ? " (a call of B = " + std::to_string(B) + " problems is refused)" : std::string());
   t += s->f32 ? "; mixed precision (fp32 storage and lane-local arithmetic, fp64 recursion and cost sums)" : "; fp64";
   t += "; backward: ";
   t += persistent ? "k_solve4 (one launch per solve)" : kind == BW_FUSED ? "k_backward4, fused matrix + gradient wavefronts" : kind == BW_FOUR ? "k_backward4, six wavefronts"
-       : kind == BW_TWO ? "k_backward2" : s->limited ? "k_backward<true> box form, one wavefront per trajectory"
+       : kind == BW_TWO ? "k_backward2" : s->modeled ? std::string("k_backward_models<") + (s->symmetric ? "true>" : "false>") +
+                                                        (s->limited ? " box form" : "") + ", one wavefront per trajectory"
+       : s->limited ? "k_backward<true> box form, one wavefront per trajectory"
        : (s->symmetric ? "k_backward<true>, one wavefront per trajectory" : "k_backward<false>, one wavefront per trajectory (general kernel)");
   if (kind == BW_FOUR || (kind == BW_FUSED && s->dev.force_general == 0 && load_B >= GFAC_MIN_LIVE))
     t += kind == BW_FOUR ? " (Q_uu factored by the gradient wavefront in launches with " + std::to_string(GFAC_MIN_LIVE) + " or more running trajectories, by the matrix wavefronts otherwise: the same bits)"
@@ -2562,13 +2693,13 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
   if (!persistent) {
     const int choice = s->dev.single_wave_rollout;
     t += "; rollout: ";
-    t += (s->integrator == 1 || s->limited || choice == 1) ? "k_rollout" : (choice == 3 || (choice == 0 && load_B <= R16_MAX_B)) ? "k_rollout16"
+    t += (s->integrator == 1 || s->limited || s->modeled || choice == 1) ? "k_rollout" : (choice == 3 || (choice == 0 && load_B <= R16_MAX_B)) ? "k_rollout16"
          : choice == 0 ? "k_rollout3 for a trajectory's first " + std::to_string(ROLLOUT16_FROM) + " rollouts, k_rollout16 from there on" : "k_rollout3";
     // (nothing of the handle is touched: the launch helpers take the batch and the record placement the call WOULD have)
     const bool tiled = records_tiled(s, B, persistent);
     const bool fused = fuse_backward_rollout(s, B, B, tiled) && s->dev.sync_every > 1;
     const int parts = s->dev.sync_every > 1 ? auto_parts(s, B) : 1;
-    const bool compact = s->dev.compaction >= 0 && s->dev.sync_every > 1 &&
+    const bool compact = s->dev.compaction >= 0 && s->dev.sync_every > 1 && !s->modeled &&
                          (s->dev.compaction == 1 || (!(fused && parts == 1) && kind != BW_ONE && tiled));
     // the round's launch form by the predicate run_solve uses: the combined launch only where the compaction does not work between its halves
     if (fused && parts == 1 && !compact)

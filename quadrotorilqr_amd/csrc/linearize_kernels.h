@@ -3,6 +3,7 @@
 // Part of the device code of libquadrotor_ilqr.so (gfx950 only); ilqr_kernels.h includes every part.
 #pragma once
 
+#include "batch_models.h"
 #include "kernels_common.h"
 
 namespace qilqr {
@@ -14,6 +15,9 @@ namespace qilqr {
 // which = 0: trajectory traj[cur[b]], 1: candidate traj[cur[b]^1].
 // need_flag: only problems whose flags contain it (0 = all).  round >= 0: publish the active count.
 // LK: layout kind of the records (se3_math.h, layout_kind).
+// Mod = BatchModels (fp64, plain records): the per-problem models extension (qilqr_set_batch_models): the dynamics half reads the model of
+// its lane's problem (batch_models.h); the cost half is unchanged.  Without it (an empty pack) the kernel takes exactly the arguments it
+// always took.
 // ---------------------------------------------------------------------------------------------
 #ifndef QILQR_LIN_BLOCK
 #define QILQR_LIN_BLOCK 128
@@ -21,10 +25,12 @@ namespace qilqr {
 #ifndef QILQR_LIN_WAVES
 #define QILQR_LIN_WAVES 3  // register budget of k_linearize in waves per SIMD: no spills (with 4, and the records' paired stores, 200-300 bytes of scratch per lane: 23.9 against 21.6 us per launch with every trajectory live, -1.7 % of a solve at B = 1024)
 #endif
-template <typename S, int LK, int INTEG, bool TILED>
+template <typename S, int LK, int INTEG, bool TILED, typename... Mod>
 __global__ __launch_bounds__(QILQR_LIN_BLOCK) __attribute__((amdgpu_waves_per_eu(QILQR_LIN_WAVES, QILQR_LIN_WAVES))) void
 k_linearize(ModelConsts<S> c, const ModelConsts<S> *__restrict__ cp, BatchState st, int B, int n, int which,
-            int need_flag, int round) {
+            int need_flag, int round, Mod... mod) {
+  constexpr bool MOD = pack_has<BatchModels, Mod...>;
+  static_assert(!MOD || (std::is_same<S, double>::value && !TILED), "the per-problem models are an fp64 extension on plain records");
   // The weights Q (144) and R (16) are more constants than a wave has scalar registers: the block keeps
   // them in LDS (filled from the device copy *cp) and the cost half reads them row by row where it uses
   // them; everything else comes from the by-value copy c.
@@ -88,8 +94,15 @@ k_linearize(ModelConsts<S> c, const ModelConsts<S> *__restrict__ cp, BatchState 
   typedef typename std::conditional<TILED, TiledRecWriter<S>, PlainRecWriter<S>>::type Writer;
   if (!cost_half) {
     const Writer wd{rec};
-    if (INTEG == 1) linearize_dynamics_rk4(c, pt, wd);  // the dense M of the Runge-Kutta extension
-    else linearize_dynamics(c, pt, wd);
+    if constexpr (MOD) {
+      // the lanes of a wavefront hold 64 problems: one record each, re-read at every knot (48 doubles a problem: from L2)
+      const ModelConsts<S> cm = problem_model(c, pack_get<BatchModels>(mod...), (long)st.row0 + b);
+      if (INTEG == 1) linearize_dynamics_rk4(cm, pt, wd);
+      else linearize_dynamics(cm, pt, wd);
+    } else {
+      if (INTEG == 1) linearize_dynamics_rk4(c, pt, wd);  // the dense M of the Runge-Kutta extension
+      else linearize_dynamics(c, pt, wd);
+    }
     wd.flush();
 #ifdef QILQR_STAMPS
     lin_stamp(0, (double)pt[0]);

@@ -3,6 +3,7 @@
 // Part of the device code of libquadrotor_ilqr.so (gfx950 only); ilqr_kernels.h includes every part.
 #pragma once
 
+#include "batch_models.h"
 #include "box_qp.h"
 #include "kernels_common.h"
 
@@ -10,20 +11,35 @@ namespace qilqr {
 
 // ---------------------------------------------------------------------------------------------
 // k_rollout: thread b.  traj[cur] + gains + alpha -> traj[cur ^ 1]
-// Lim = ControlLimits (fp64): the thrust-limit extension, controls clamped to the box (rollout_problem<.., LIM>).  Without it (an
-// empty pack) the kernel takes exactly the arguments it always took.
+// Lim = ControlLimits (fp64): the thrust-limit extension, controls clamped to the box (rollout_problem<.., LIM>).  Lim = BatchModels
+// (fp64): the per-problem models extension, each lane steps with its problem's model (batch_models.h), loaded once per launch.  Either,
+// both (ControlLimits first), or neither: without them (an empty pack) the kernel takes exactly the arguments it always took.
 // ---------------------------------------------------------------------------------------------
 template <typename S, int INTEG, typename... Lim>
 __global__ __launch_bounds__(64) void k_rollout(ModelConsts<S> c, BatchState st, int B, int n,
                                                 int need_flag, Lim... lim) {
-  constexpr bool LIM = sizeof...(Lim) == 1;
+  constexpr bool LIM = pack_has<ControlLimits, Lim...>;
+  constexpr bool MOD = pack_has<BatchModels, Lim...>;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   if (need_flag && !(st.flags[b] & need_flag)) return;
   const int cur = st.cur[b];
-  if constexpr (LIM) {
+  if constexpr (MOD) {
+    static_assert(std::is_same<S, double>::value, "the per-problem models are an fp64 extension");
+    const ModelConsts<S> cm = problem_model(c, pack_get<BatchModels>(lim...), (long)st.row0 + b);
+    if constexpr (LIM) {
+      const ControlLimits &L = pack_get<ControlLimits>(lim...);
+      rollout_problem<true, S, INTEG, true>(cm, (const S *)st.traj[cur] + knot_base<true>(b, n, 18),
+                                            (const S *)st.gains + knot_base<true>(b, n, 52), (S)st.alpha[b],
+                                            (S *)st.traj[cur ^ 1] + knot_base<true>(b, n, 18), n, L.lo, L.hi);
+    } else {
+      rollout_problem<true, S, INTEG>(cm, (const S *)st.traj[cur] + knot_base<true>(b, n, 18),
+                                      (const S *)st.gains + knot_base<true>(b, n, 52), (S)st.alpha[b],
+                                      (S *)st.traj[cur ^ 1] + knot_base<true>(b, n, 18), n);
+    }
+  } else if constexpr (LIM) {
     static_assert(std::is_same<S, double>::value, "the thrust limits are an fp64 extension");
-    const ControlLimits &L = (lim, ...);
+    const ControlLimits &L = pack_get<ControlLimits>(lim...);
     rollout_problem<true, S, INTEG, true>(c, (const S *)st.traj[cur] + knot_base<true>(b, n, 18),
                                           (const S *)st.gains + knot_base<true>(b, n, 52), (S)st.alpha[b],
                                           (S *)st.traj[cur ^ 1] + knot_base<true>(b, n, 18), n, L.lo, L.hi);

@@ -319,6 +319,24 @@ int qilqr_set_control_limits(qilqr_solver *s, const double *lo, const double *hi
  * models = NULL with B = 0 clears them: every result is then again the handle's without them. */
 int qilqr_set_batch_models(qilqr_solver *s, const qilqr_model *models, int32_t B);
 
+/* Spherical obstacles -- an EXTENSION: a soft penalty in the cost of every entry point that evaluates or differentiates it
+ * (qilqr_solve, qilqr_solve_batch[_device], qilqr_cost_trajectory, qilqr_backwards_pass, qilqr_line_search, and so
+ * qilqr_cost_history), shared by every problem of the handle.  spheres is count x 5 doubles {cx, cy, cz, radius, weight}.
+ * At every knot i (the last included), with p the knot's position, d_j = |p - c_j| and h_j = radius_j - d_j, the knot cost becomes
+ *     tracking_cost + sum_j weight_j h_j^2   over the spheres with h_j > 0, added in index order after the tracking cost.
+ * A sphere with h_j <= 0 does no arithmetic on the result: obstacles that no knot reaches give the bits of a handle without them.
+ * Differentials (tangent order [rho, theta, dv, dw], the reference's factor 2): with R the knot's attitude, n_j = (p - c_j) / d_j and
+ * m_j = R^T n_j, C_x[0:3] += -2 weight_j h_j m_j and C_xx[0:3, 0:3] += 2 weight_j m_j m_j^T (Gauss-Newton, as the tracking cost's
+ * Hessian: Q_xx stays positive semi-definite).  d_j == 0 exactly: the cost term is weight_j radius_j^2 and the differentials get
+ * nothing (the direction is undefined).  Composes with either integrator, restarts, thrust limits, per-problem models, any weights,
+ * force_general, the compaction and sub-batch streams; the rounds take k_backward_rollout + k_linearize or three launches where they
+ * would have taken the one-launch round kernel (the same bits).  Validates, uploads the table once, and waits for the handle's stream.
+ * QILQR_ERR_INVALID_ARG for count > QILQR_MAX_OBSTACLES, a non-finite value, radius <= 0, weight < 0, a mixed-precision handle
+ * (precision = 1), and, while obstacles are set, a solve with persistent = 1.  spheres = NULL with count = 0 clears them: every
+ * result is then again the handle's without them. */
+#define QILQR_MAX_OBSTACLES 64
+int qilqr_set_obstacles(qilqr_solver *s, const double *spheres, int32_t count);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -404,6 +422,10 @@ int qilqr_sharded_set_transport(qilqr_sharded *h, int32_t transport);
  * sharded solves (qilqr_solve_batch_sharded, qilqr_solve_batch_sharded_device) refuse another B.  The models are checked for the whole
  * batch first (the index in an error is the batch's); a failure leaves every shard without models.  NULL, 0 clears them. */
 int qilqr_sharded_set_batch_models(qilqr_sharded *h, const qilqr_model *models, int32_t B);
+
+/* qilqr_set_obstacles on every shard's solver (the same spheres for the whole batch); checked once first, and a failure leaves
+ * every shard without obstacles.  NULL, 0 clears them. */
+int qilqr_sharded_set_obstacles(qilqr_sharded *h, const double *spheres, int32_t count);
 const char *qilqr_sharded_transport(qilqr_sharded *h);
 int qilqr_solve_batch_sharded_device(qilqr_sharded *h, const double *init, const double *desired_batch, int32_t B, int32_t n,
                                      int32_t root, double *d_out_traj, double *d_out_cost, int32_t *d_out_status,
@@ -433,8 +455,8 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
 
 /* ABI version of this header: 7 (qilqr_device_config grew by round_launch, rounds_per_launch, fuse_in_flight, dense_weights -- the
  * switches that were environment variables -- and the *_sized entry points carry the caller's structure size; version 6 added
- * `compaction`).  qilqr_set_control_limits, QILQR_STATUS_QP_FAILED, qilqr_set_batch_models and qilqr_sharded_set_batch_models were added
- * within version 7: no structure changed. */
+ * `compaction`).  qilqr_set_control_limits, QILQR_STATUS_QP_FAILED, qilqr_set_batch_models, qilqr_sharded_set_batch_models,
+ * qilqr_set_obstacles, qilqr_sharded_set_obstacles and QILQR_MAX_OBSTACLES were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

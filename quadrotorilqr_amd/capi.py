@@ -32,6 +32,7 @@ STATUS_CONVERGED = 1
 STATUS_MAX_ITERS = 2
 STATUS_LINE_SEARCH_FAILED = 3
 STATUS_QP_FAILED = 4  # extension: a knot's box QP broke down (set_control_limits)
+MAX_OBSTACLES = 64  # QILQR_MAX_OBSTACLES: spheres per handle (set_obstacles)
 
 # every symbol include/quadrotor_ilqr.h declares
 EXPORTS = (
@@ -39,6 +40,7 @@ EXPORTS = (
     "qilqr_solve_batch_device", "qilqr_cost_trajectory", "qilqr_backwards_pass", "qilqr_forward_sim",
     "qilqr_line_search", "qilqr_cost_history", "qilqr_profile_reset", "qilqr_profile_get", "qilqr_profile_mode", "qilqr_set_regularisation",
     "qilqr_set_integrator", "qilqr_set_control_limits", "qilqr_set_batch_models", "qilqr_sharded_set_batch_models",
+    "qilqr_set_obstacles", "qilqr_sharded_set_obstacles",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -102,6 +104,8 @@ def load():
         lib.qilqr_set_control_limits.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         lib.qilqr_set_batch_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         lib.qilqr_sharded_set_batch_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.qilqr_set_obstacles.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
+        lib.qilqr_sharded_set_obstacles.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
         _lib = lib
     return _lib
 
@@ -200,6 +204,15 @@ def model_array(models):
         m.arm_length_m = cols["arm_length_m"][b]
         m.torque_to_thrust_ratio_m = cols["torque_to_thrust_ratio_m"][b]
         m.g_mpss = cols["g_mpss"][b]
+    return arr
+
+
+def obstacle_array(spheres):
+    """(K, 5) float64 rows {cx, cy, cz, radius, weight} for qilqr_set_obstacles (the library checks the values)"""
+    arr = _d(spheres)
+    if arr.ndim != 2 or arr.shape[1] != 5 or arr.shape[0] == 0:
+        raise TypeError(f"obstacles: a (K, 5) array of spheres {{cx, cy, cz, radius, weight}}, K >= 1; got shape {arr.shape} "
+                        "(clear_obstacles() switches them off)")
     return arr
 
 
@@ -458,6 +471,19 @@ class QuadrotorILQRBatch:
         if rc:
             _raise(rc)
 
+    def set_obstacles(self, spheres):
+        """Spherical obstacles penalised in the cost (an extension): `spheres` is a (K, 5) array of {cx, cy, cz, radius, weight}, K <= 64,
+        shared by every problem -- see qilqr_set_obstacles in include/quadrotor_ilqr.h.  clear_obstacles() switches them off again."""
+        arr = obstacle_array(spheres)
+        rc = load().qilqr_set_obstacles(self._h, _p(arr), C.c_int32(len(arr)))
+        if rc:
+            _raise(rc)
+
+    def clear_obstacles(self):
+        rc = load().qilqr_set_obstacles(self._h, None, C.c_int32(0))
+        if rc:
+            _raise(rc)
+
     def profile_get(self):
         p = Profile()
         rc = load().qilqr_profile_get(self._h, C.byref(p))
@@ -539,6 +565,18 @@ class QuadrotorILQRSharded:
 
     def clear_models(self):
         rc = load().qilqr_sharded_set_batch_models(self._h, None, C.c_int32(0))
+        if rc:
+            _raise(rc)
+
+    def set_obstacles(self, spheres):
+        """QuadrotorILQRBatch.set_obstacles on every shard's solver (qilqr_sharded_set_obstacles)"""
+        arr = obstacle_array(spheres)
+        rc = load().qilqr_sharded_set_obstacles(self._h, _p(arr), C.c_int32(len(arr)))
+        if rc:
+            _raise(rc)
+
+    def clear_obstacles(self):
+        rc = load().qilqr_sharded_set_obstacles(self._h, None, C.c_int32(0))
         if rc:
             _raise(rc)
 

@@ -72,6 +72,9 @@ struct qilqr_solver {
   bool modeled = false;         // per-problem models set (qilqr_set_batch_models): the general route, every call of exactly models_B problems
   long models_B = 0;            // ... for how many problems
   double *d_models = nullptr;   // ... their records in device memory, [models_B][PM_WORDS] (batch_models.h)
+  int n_obstacles = 0;          // spherical obstacles in the cost (qilqr_set_obstacles): k_linearize adds them, k_round never runs
+  double *d_obstacles = nullptr;   // ... the table in device memory, [OB_MAX][OB_WORDS] (obstacles.h), allocated at the first setter call
+  std::vector<double> obstacles;   // ... and its host copy (qilqr_describe)
   ModelConsts<float> constsf;   // the model constants for the fp32 lane-local kernels
   // workspace
   long cap_B = 0, cap_n = 0;
@@ -421,6 +424,46 @@ int launch_linearize(qilqr_solver *s, long B, long n, int which, int need_flag, 
   launch(s, K_LINEARIZE, (k_linearize<S, LK, 0, TILED>), grid, dim3(QILQR_LIN_BLOCK), CONSTS, DCONSTS, s->st, (int)B, (int)n, which, need_flag, round)
 #define QILQR_LAUNCH_LIN_RK4(LK) \
   launch(s, K_LINEARIZE, (k_linearize<double, LK, 1, false>), grid, dim3(QILQR_LIN_BLOCK), s->consts, (const ModelConsts<double> *)s->d_consts, s->st, (int)B, (int)n, which, need_flag, round)
+  if (s->n_obstacles > 0) {  // the obstacle extension (fp64): the same record kinds and placements, the penalties added by the cost half
+    const Obstacles ob{s->d_obstacles, s->n_obstacles};
+    const int lk = (s->integrator == 0 && layout_kind(s->layout) == 2 && s->q_diag) ? 3 : layout_kind(s->layout);
+#define QILQR_LAUNCH_LIN_OBS(LK, INTEG, TILED, ...)                                                                                         \
+  launch(s, K_LINEARIZE, (k_linearize<double, LK, INTEG, TILED, __VA_ARGS__>), grid, dim3(QILQR_LIN_BLOCK), s->consts,                  \
+         (const ModelConsts<double> *)s->d_consts, s->st, (int)B, (int)n, which, need_flag, round, MOD_ARGS)
+    if (s->modeled) {  // ... beside the per-problem models (plain placement)
+      const ModelsObstacles mo{BatchModels{s->d_models}, ob};
+#define MOD_ARGS mo
+      switch (lk + (s->integrator == 1 ? 4 : 0)) {
+        case 0: QILQR_LAUNCH_LIN_OBS(0, 0, false, ModelsObstacles); break;
+        case 1: QILQR_LAUNCH_LIN_OBS(1, 0, false, ModelsObstacles); break;
+        case 2: QILQR_LAUNCH_LIN_OBS(2, 0, false, ModelsObstacles); break;
+        case 3: QILQR_LAUNCH_LIN_OBS(3, 0, false, ModelsObstacles); break;
+        case 4: QILQR_LAUNCH_LIN_OBS(0, 1, false, ModelsObstacles); break;
+        case 5: QILQR_LAUNCH_LIN_OBS(1, 1, false, ModelsObstacles); break;
+        default: QILQR_LAUNCH_LIN_OBS(2, 1, false, ModelsObstacles); break;
+      }
+#undef MOD_ARGS
+      return QILQR_OK;
+    }
+#define MOD_ARGS ob
+    // (the dense kind 0 is non-symmetric weights: the one-wavefront backward kernel, plain records -- records_tiled)
+    if (s->st.layout.tiled && (lk == 0 || s->integrator == 1)) return fail(QILQR_ERR_INVALID_ARG, "obstacles: no tiled records of this kind");
+    switch (lk + (s->integrator == 1 ? 4 : 0) + (s->st.layout.tiled ? 8 : 0)) {
+      case 0: QILQR_LAUNCH_LIN_OBS(0, 0, false, Obstacles); break;
+      case 1: QILQR_LAUNCH_LIN_OBS(1, 0, false, Obstacles); break;
+      case 2: QILQR_LAUNCH_LIN_OBS(2, 0, false, Obstacles); break;
+      case 3: QILQR_LAUNCH_LIN_OBS(3, 0, false, Obstacles); break;
+      case 4: QILQR_LAUNCH_LIN_OBS(0, 1, false, Obstacles); break;
+      case 5: QILQR_LAUNCH_LIN_OBS(1, 1, false, Obstacles); break;
+      case 6: QILQR_LAUNCH_LIN_OBS(2, 1, false, Obstacles); break;
+      case 9: QILQR_LAUNCH_LIN_OBS(1, 0, true, Obstacles); break;
+      case 10: QILQR_LAUNCH_LIN_OBS(2, 0, true, Obstacles); break;
+      default: QILQR_LAUNCH_LIN_OBS(3, 0, true, Obstacles); break;
+    }
+#undef MOD_ARGS
+#undef QILQR_LAUNCH_LIN_OBS
+    return QILQR_OK;
+  }
   if (s->modeled) {  // the per-problem models extension: fp64, plain placement (the one-wavefront backward kernel reads the records)
     const BatchModels bm{s->d_models};
 #define QILQR_LAUNCH_LIN_MOD(LK, INTEG)                                                                                                     \
@@ -654,7 +697,7 @@ bool fuse_kinds(const qilqr_solver *s, long B, long total_B, bool tiled) {
   // (force_general = 8 with the combined launch: k_round with the six-wavefront backward pass in EVERY launch -- tests, A/B)
   if (!(s->dev.force_general == 0 || s->dev.force_general == 5 || s->dev.force_general == 8)) return false;
   if (s->dev.force_general != 8 && backward_kind(s, load_B) != BW_FUSED) return false;
-  if (s->dev.force_general == 8 && (s->dev.round_launch != 0 || s->f32)) return false;  // (only k_round has the form: not k_backward_rollout)
+  if (s->dev.force_general == 8 && (s->dev.round_launch != 0 || s->f32 || s->n_obstacles > 0)) return false;  // (only k_round has the form: not k_backward_rollout)
   if (!(s->dev.single_wave_rollout == 0 || s->dev.single_wave_rollout == 3) || load_B > R16_MAX_B) return false;
   return true;
 }
@@ -681,7 +724,9 @@ struct InFlight {
 };
 // k_round (round_kernels.h): the combined launch and the linearisation of its candidates in one.  fp64 storage only (the mixed mode keeps
 // the two launches).  The round's counts go into the counter set of its parity; the launch publishes the round before it.
-bool round_kernel_ok(const qilqr_solver *s) { return s->dev.round_launch == 0 && !s->f32; }
+// A handle with obstacles keeps the two launches as well: k_round linearises with linearize_cost alone (the same bits as
+// k_backward_rollout + k_linearize, round_kernels.h), and only k_linearize adds the penalties.
+bool round_kernel_ok(const qilqr_solver *s) { return s->dev.round_launch == 0 && !s->f32 && s->n_obstacles == 0; }
 // rounds per launch of k_round where a launch may hold several (qilqr_device_config.rounds_per_launch = 1, 2 or 4: A/B; 0 = 4)
 int rounds_per_launch(const qilqr_solver *s) {
   const int v = s->dev.rounds_per_launch;
@@ -1307,7 +1352,7 @@ int check_quaternions(const double *traj, long count, const char *what) {
 bool use_persistent(const qilqr_solver *s, long B) {
   (void)B;
 #ifdef QILQR_WITH_SOLVE4
-  return s->symmetric && s->dev.persistent == 1 && s->integrator == 0 && !s->limited && !s->modeled;
+  return s->symmetric && s->dev.persistent == 1 && s->integrator == 0 && !s->limited && !s->modeled && s->n_obstacles == 0;
 #else
   (void)s;
   return false;  // k_solve4 is in the diagnostics build (qilqr_create refuses persistent = 1 here)
@@ -1344,6 +1389,8 @@ int solve_batch_device_impl(qilqr_solver *s, const double *d_init, const double 
     return fail(QILQR_ERR_INVALID_ARG, "control limits: persistent = 1 (k_solve4) has no box form; take the rounds (persistent = 0)");
   if (s->modeled && s->dev.persistent == 1)
     return fail(QILQR_ERR_INVALID_ARG, "batch models: persistent = 1 (k_solve4) has one model for the batch; take the rounds (persistent = 0)");
+  if (s->n_obstacles > 0 && s->dev.persistent == 1)
+    return fail(QILQR_ERR_INVALID_ARG, "obstacles: persistent = 1 (k_solve4) linearises without them; take the rounds (persistent = 0)");
   const RoctxRange range(s, "batch solve, trajectories:", (long)B);
   int rc = begin_batch(s, B, n, d_desired_batch);
   if (rc) return rc;
@@ -1622,6 +1669,7 @@ void qilqr_destroy(qilqr_solver *s) {
   if (s->d_desired) (void)hipFree(s->d_desired);
   if (s->d_ctab) (void)hipFree(s->d_ctab);
   if (s->d_models) (void)hipFree(s->d_models);
+  if (s->d_obstacles) (void)hipFree(s->d_obstacles);
   if (s->d_consts) (void)hipFree(s->d_consts);
   if (s->h_counters) (void)hipHostFree(s->h_counters);
   if (s->h_active) (void)hipHostFree(s->h_active);
@@ -1777,6 +1825,42 @@ int qilqr_set_batch_models(qilqr_solver *s, const qilqr_model *models, int32_t B
     HIP_TRY(hipMemcpy(s->d_models, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
     s->modeled = true;
     s->models_B = B;
+  }
+  return QILQR_OK;
+}
+
+namespace {
+// qilqr_set_obstacles' checks of a table, shared with the sharded setter
+int check_obstacles(const double *spheres, int32_t count) {
+  if (count < 0 || count > QILQR_MAX_OBSTACLES || (spheres == nullptr) != (count == 0))
+    return fail(QILQR_ERR_INVALID_ARG, "obstacles: 1 ... " + std::to_string(QILQR_MAX_OBSTACLES) +
+                                           " spheres {cx, cy, cz, radius, weight}, or spheres = NULL and count = 0 to clear them");
+  for (int32_t j = 0; j < count; ++j) {
+    const double *sp = spheres + (size_t)j * OB_WORDS;
+    for (int k = 0; k < OB_WORDS; ++k)
+      if (!std::isfinite(sp[k])) return fail(QILQR_ERR_INVALID_ARG, "obstacles: sphere " + std::to_string(j) + " has a non-finite value");
+    if (!(sp[OB_RADIUS] > 0.0)) return fail(QILQR_ERR_INVALID_ARG, "obstacles: sphere " + std::to_string(j) + " has radius <= 0");
+    if (!(sp[OB_WEIGHT] >= 0.0)) return fail(QILQR_ERR_INVALID_ARG, "obstacles: sphere " + std::to_string(j) + " has weight < 0");
+  }
+  return QILQR_OK;
+}
+}  // namespace
+
+static_assert(OB_MAX == QILQR_MAX_OBSTACLES, "obstacles.h and the C header agree on the table size");
+int qilqr_set_obstacles(qilqr_solver *s, const double *spheres, int32_t count) {
+  if (!s) return fail(QILQR_ERR_INVALID_ARG, "null solver");
+  int rc = check_obstacles(spheres, count);
+  if (rc) return rc;
+  if (count > 0 && s->f32)
+    return fail(QILQR_ERR_INVALID_ARG, "obstacles need precision 0 (fp64): the mixed-precision kernels have no obstacle form");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));  // (no launch of this handle still reads the table)
+  s->n_obstacles = 0;
+  s->obstacles.assign(spheres, spheres + (size_t)count * OB_WORDS);
+  if (count > 0) {
+    if (!s->d_obstacles) HIP_TRY(hipMalloc((void **)&s->d_obstacles, sizeof(double) * OB_MAX * OB_WORDS));
+    HIP_TRY(hipMemcpy(s->d_obstacles, spheres, sizeof(double) * (size_t)count * OB_WORDS, hipMemcpyHostToDevice));
+    s->n_obstacles = count;
   }
   return QILQR_OK;
 }
@@ -2480,6 +2564,23 @@ int qilqr_sharded_set_batch_models(qilqr_sharded *h, const qilqr_model *models, 
   return QILQR_OK;
 }
 
+int qilqr_sharded_set_obstacles(qilqr_sharded *h, const double *spheres, int32_t count) {
+  if (!h || h->solvers.empty()) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  int rc = check_obstacles(spheres, count);  // (checked once, before any shard changes)
+  if (rc) return rc;
+  if (count > 0 && h->solvers[0]->f32)
+    return fail(QILQR_ERR_INVALID_ARG, "obstacles need precision 0 (fp64): the mixed-precision kernels have no obstacle form");
+  DeviceGuard guard;
+  for (qilqr_solver *s : h->solvers) {
+    if ((rc = qilqr_set_obstacles(s, spheres, count))) {  // (none half set: every shard cleared)
+      const std::string msg = g_last_error;
+      for (qilqr_solver *q : h->solvers) (void)qilqr_set_obstacles(q, nullptr, 0);
+      return fail(rc, msg);
+    }
+  }
+  return QILQR_OK;
+}
+
 int qilqr_sharded_set_transport(qilqr_sharded *h, int32_t transport) {
   if (!h) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   if (transport != QILQR_TRANSPORT_AUTO && transport != QILQR_TRANSPORT_RCCL && transport != QILQR_TRANSPORT_PEER_COPY)
@@ -2680,6 +2781,16 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
   if (s->modeled)
     t += "; per-problem models (extension): " + std::to_string(s->models_B) + " problems, each with its own mass, g, inertia and moment arms" +
          (B != s->models_B ? " (a call of B = " + std::to_string(B) + " problems is refused)" : std::string());
+  if (s->n_obstacles > 0) {
+    t += "; obstacles (extension): " + std::to_string(s->n_obstacles) + " sphere(s) {center; radius, weight} =";
+    for (int j = 0; j < s->n_obstacles; ++j) {
+      const double *sp = s->obstacles.data() + (size_t)j * OB_WORDS;
+      char one[160];
+      std::snprintf(one, sizeof one, "%s {%g, %g, %g; %g, %g}", j ? "," : "", sp[0], sp[1], sp[2], sp[OB_RADIUS], sp[OB_WEIGHT]);
+      t += one;
+    }
+    t += ", penalised in the knot cost by k_linearize (the rounds never take the kernels that linearise inside themselves)";
+  }
   t += s->f32 ? "; mixed precision (fp32 storage and lane-local arithmetic, fp64 recursion and cost sums)" : "; fp64";
   t += "; backward: ";
   t += persistent ? "k_solve4 (one launch per solve)" : kind == BW_FUSED ? "k_backward4, fused matrix + gradient wavefronts" : kind == BW_FOUR ? "k_backward4, six wavefronts"
@@ -2706,9 +2817,13 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
       t += round_kernel_ok(s) ? "; round: one launch (k_round), " + std::to_string(rounds_per_launch(s)) + " rounds per launch, while no other batch solve of the process is in flight on the device"
                                : std::string("; round: k_backward_rollout + k_linearize");
     else if (compact && fuse_kinds(s, B, B, tiled))
-      t += "; round: three launches while the compaction runs, then k_round (the mixed mode: k_backward_rollout + k_linearize) once the running trajectories fit " + std::to_string(std::min(parts, 3)) + " block(s) of four per CU";
+      t += "; round: three launches while the compaction runs, then " +
+           std::string(s->n_obstacles > 0 ? "k_backward_rollout + k_linearize (obstacles)" : "k_round (the mixed mode: k_backward_rollout + k_linearize)") +
+           " once the running trajectories fit " + std::to_string(std::min(parts, 3)) + " block(s) of four per CU";
     else if (long from = 0; compact && s->dev.compaction != 1 && late_tail_kinds(s, B, B, tiled, &from))
-      t += "; round: three launches, then k_round (the same bits; the mixed mode: k_backward_rollout + k_linearize) once the running trajectories fit " + std::to_string(std::min(parts, 3)) + " block(s) of four per CU"
+      t += "; round: three launches, then " +
+           std::string(s->n_obstacles > 0 ? "k_backward_rollout + k_linearize (the same bits; obstacles)" : "k_round (the same bits; the mixed mode: k_backward_rollout + k_linearize)") +
+           " once the running trajectories fit " + std::to_string(std::min(parts, 3)) + " block(s) of four per CU"
            + (from > 0 ? " and the rollouts are k_rollout16's (round " + std::to_string(from) + " on)" : std::string());
     else
       t += "; round: three launches";

@@ -5,6 +5,7 @@
 
 #include "batch_models.h"
 #include "kernels_common.h"
+#include "obstacles.h"
 
 namespace qilqr {
 
@@ -18,6 +19,10 @@ namespace qilqr {
 // Mod = BatchModels (fp64, plain records): the per-problem models extension (qilqr_set_batch_models): the dynamics half reads the model of
 // its lane's problem (batch_models.h); the cost half is unchanged.  Without it (an empty pack) the kernel takes exactly the arguments it
 // always took.
+// Mod = Obstacles (fp64, either placement), or ModelsObstacles (plain, with the per-problem models): the obstacle extension (qilqr_set_obstacles): the
+// cost half adds the spheres' penalties (obstacles.h) to the knot cost, C_x and the pose block of C_xx behind linearize_cost, in the
+// record positions of the layout kind.  The table sits in LDS, one copy per cost wavefront, filled beside Q and R: the obstacle index
+// is wave-uniform, so every lane reads the same word.
 // ---------------------------------------------------------------------------------------------
 #ifndef QILQR_LIN_BLOCK
 #define QILQR_LIN_BLOCK 128
@@ -25,12 +30,19 @@ namespace qilqr {
 #ifndef QILQR_LIN_WAVES
 #define QILQR_LIN_WAVES 3  // register budget of k_linearize in waves per SIMD: no spills (with 4, and the records' paired stores, 200-300 bytes of scratch per lane: 23.9 against 21.6 us per launch with every trajectory live, -1.7 % of a solve at B = 1024)
 #endif
+// the obstacle table of the calling cost wavefront (k_linearize with Obstacles only: no other kernel references it)
+__device__ __forceinline__ double *lin_obstacle_lds() {
+  __shared__ double tab[QILQR_LIN_BLOCK / 64][OB_MAX * OB_WORDS];
+  return tab[threadIdx.x >> 6];
+}
 template <typename S, int LK, int INTEG, bool TILED, typename... Mod>
 __global__ __launch_bounds__(QILQR_LIN_BLOCK) __attribute__((amdgpu_waves_per_eu(QILQR_LIN_WAVES, QILQR_LIN_WAVES))) void
 k_linearize(ModelConsts<S> c, const ModelConsts<S> *__restrict__ cp, BatchState st, int B, int n, int which,
             int need_flag, int round, Mod... mod) {
-  constexpr bool MOD = pack_has<BatchModels, Mod...>;
+  constexpr bool MOD = pack_has<BatchModels, Mod...> || pack_has<ModelsObstacles, Mod...>;
   static_assert(!MOD || (std::is_same<S, double>::value && !TILED), "the per-problem models are an fp64 extension on plain records");
+  constexpr bool OBS = pack_has<Obstacles, Mod...> || pack_has<ModelsObstacles, Mod...>;
+  static_assert(!OBS || std::is_same<S, double>::value, "the obstacles are an fp64 extension");
   // The weights Q (144) and R (16) are more constants than a wave has scalar registers: the block keeps
   // them in LDS (filled from the device copy *cp) and the cost half reads them row by row where it uses
   // them; everything else comes from the by-value copy c.
@@ -81,6 +93,11 @@ k_linearize(ModelConsts<S> c, const ModelConsts<S> *__restrict__ cp, BatchState 
   if (cost_half) {  // wave-uniform (per_half is a multiple of 64)
     const int wl = threadIdx.x & 63;
     for (int k = wl; k < 160; k += 64) qr[k] = (k < 144) ? cp->Q[k] : cp->R[k - 144];
+    if constexpr (OBS) {
+      const Obstacles &ob = pack_obstacles(mod...);
+      double *ot = lin_obstacle_lds();
+      for (int k = wl; k < ob.count * OB_WORDS; k += 64) ot[k] = ob.tab[k];
+    }
     __builtin_amdgcn_wave_barrier();  // written and read by this wavefront only (LDS operations of a wave stay in order)
   }
   if (b >= B) return;
@@ -96,7 +113,7 @@ k_linearize(ModelConsts<S> c, const ModelConsts<S> *__restrict__ cp, BatchState 
     const Writer wd{rec};
     if constexpr (MOD) {
       // the lanes of a wavefront hold 64 problems: one record each, re-read at every knot (48 doubles a problem: from L2)
-      const ModelConsts<S> cm = problem_model(c, pack_get<BatchModels>(mod...), (long)st.row0 + b);
+      const ModelConsts<S> cm = problem_model(c, pack_models(mod...), (long)st.row0 + b);
       if (INTEG == 1) linearize_dynamics_rk4(cm, pt, wd);
       else linearize_dynamics(cm, pt, wd);
     } else {
@@ -114,8 +131,32 @@ k_linearize(ModelConsts<S> c, const ModelConsts<S> *__restrict__ cp, BatchState 
   S pd[18];
   if (st.desired_tiled) load_knot<true>((const S *)st.desired + knot_base<true>(b, n, 18), i, 18, pd);
   else load_knot<false>((const S *)st.desired, i, 18, pd);
-  const S cost = linearize_cost<LK>(qr, qr + 144, pt, pd, w);
+  S cost = linearize_cost<LK>(qr, qr + 144, pt, pd, w);
   w.flush();
+  if constexpr (OBS) {
+    // the penalties, added to what linearize_cost stored (read back only for a knot that an obstacle reaches)
+    constexpr RecLayout L = make_layout(LK > 0, LK >= 2);
+    S *const rc = w.rec;
+    auto at = [&](int k) -> S & { return TILED ? rc[(k >> 1) * TILE2 + (k & 1)] : rc[k]; };
+    auto cxx = [&](int k, int l) {  // where C_xx[k][l] (k, l < 3) lives: both triangles in the dense kind, the upper one otherwise
+      return LK == 0 ? L.off_cxx + 12 * k + l : L.off_cxx + symrow_index(LK == 1, k < l ? k : l, k < l ? l : k);
+    };
+    S g[3], H[9];
+    const auto load = [&] {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g[k] = at(L.off_g + k);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) H[k] = at(cxx(k / 3, k % 3));
+    };
+    if (add_obstacles((const S *)lin_obstacle_lds(), pack_obstacles(mod...).count, pt, cost, g, H, load)) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) at(L.off_g + k) = g[k];
+#pragma unroll
+      for (int k = 0; k < 9; ++k)
+        if (LK == 0 || k / 3 <= k % 3) at(cxx(k / 3, k % 3)) = H[k];
+      at(L.off_cost) = cost;
+    }
+  }
   st.knot_cost[buf][cost_index(b, i, n)] = (double)cost;  // summed in fp64 (k_init / k_backward)
 #ifdef QILQR_STAMPS
   lin_stamp(1, (double)cost);

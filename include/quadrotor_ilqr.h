@@ -134,7 +134,7 @@ typedef struct {
   int32_t streams; /* batch solves with sync_every > 1: number of contiguous sub-batches that run their rounds on
                       their own HIP streams (their kernels are bound by different resources and overlap);
                       0 = automatic (1 below 4096 trajectories, 2 at 4096, beyond 4 when the process runs with
-                      GPU_MAX_HW_QUEUES >= 8 and 2 otherwise: see auto_parts in ilqr_capi.hip), at most 8 */
+                      GPU_MAX_HW_QUEUES >= 8 and 2 otherwise: see auto_parts in route.h), at most 8 */
   int32_t persistent; /* the solve as ONE launch (k_solve4: blocks of eight wavefronts own four trajectories each from the
                          first linearisation to the exit status, no rounds, no host in the loop; symmetric weights only):
                          0 = the rounds of three launches at every batch size (by measurement they are level or ahead at every size

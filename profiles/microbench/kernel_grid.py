@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic: whole-solve rate for every pair (backward kernel, rollout kernel) at large batches -- where the automatic
-choices (ilqr_capi.hip: backward_kind, launch_rollout) should change.
+choices (route.h: backward_kind, plan_route) should change.
 usage (from the repository root): PYTHONPATH=. python3 profiles/microbench/kernel_grid.py [B ...]"""
 import sys, time
 import torch

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic: whole-solve rate by the number of sub-batches on their own streams (qilqr_device_config.streams) at large
-batches -- where auto_parts (ilqr_capi.hip) should put its thresholds.
+batches -- where auto_parts (route.h) should put its thresholds.
 usage (from the repository root): PYTHONPATH=. python3 profiles/microbench/streams_sweep.py [B ...]"""
 import os, sys, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")

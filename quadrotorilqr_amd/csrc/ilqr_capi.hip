@@ -23,6 +23,7 @@
 #include "../../include/quadrotor_ilqr.h"
 #include "host_model.h"
 #include "ilqr_kernels.h"
+#include "route.h"
 
 using namespace qilqr;
 
@@ -86,12 +87,13 @@ struct qilqr_solver {
   // whole batch on the main stream, parts 1..MAX_PARTS are sub-batches on their own streams
   unsigned long long *h_active = nullptr;
   unsigned long long *d_active = nullptr;  // the same memory as the device sees it
-  static constexpr int MAX_PARTS = 8;
+  static constexpr int MAX_PARTS = qilqr::MAX_PARTS;
   hipStream_t part_stream[MAX_PARTS] = {};
   hipEvent_t part_done[MAX_PARTS] = {};
   hipEvent_t main_ready = nullptr;
   int *d_part_counters = nullptr;  // [MAX_PARTS][2][COUNT_WORDS]
-  long total_B = 0;                // trajectories in flight on the device in this call (kernel choices go by it)
+  long total_B = 0;                // trajectories in flight on the device in this call
+  Route route;                     // the kernels this call takes (route.h): planned by begin_batch
   bool round_captured = false;     // the round just enqueued was a k_round launch (it fills the single solve's debug ring itself)
   long live_hint = 0;              // trajectories known to be running in this call right now (0: unknown, take the batch): launch_backward
   double *io_aos = nullptr;         // device scratch in the plain [B][n][W] layout (W <= 52), for host I/O (lazy)
@@ -313,12 +315,6 @@ int ensure_workspace(qilqr_solver *s, long B, long n) {
   return QILQR_OK;
 }
 
-inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
-#ifndef QILQR_REGIME_B
-#define QILQR_REGIME_B 4096
-#endif
-constexpr long REGIME_B = QILQR_REGIME_B;  // calls with more trajectories in flight take the kernels built for a full chip
-constexpr long R16_MAX_B = REGIME_B;  // k_rollout16 for every rollout up to this many trajectories (launch_rollout)
 // largest number of consecutive restarts lm_restart (kernels_common.h) can grant one iteration
 inline double max_restarts(const SolveParams &p) {
   if (!(p.mu_init > 0.0) || !(p.mu_init <= p.mu_max)) return 0.0;
@@ -347,22 +343,50 @@ int from_tiled(qilqr_solver *s, double *d_plain, void *t0, void *t1, const int *
   return QILQR_OK;
 }
 
-// bind the desired trajectory (shared, or per problem: plain device array, re-tiled here) and reset
-// the buffer selectors
-bool use_persistent(const qilqr_solver *s, long B);
-bool records_tiled(const qilqr_solver *s, long load_B, bool persistent);
-// per-problem models (qilqr_set_batch_models): problem b reads record b, so every computing call is over the rows they were set for
-int check_batch_models(const qilqr_solver *s, long B) {
-  if (s->modeled && B != s->models_B)
+// hardware queues HIP multiplexes this process's streams onto: GPU_MAX_HW_QUEUES as the runtime read it at start-up (default 4)
+// Latched at the first qilqr_create_sized of the process, which calls it (the runtime reads the variable once, when it starts: a value
+// put into the environment later -- os.environ after the first GPU call -- changes nothing in the runtime and must change nothing here)
+int hw_queues() {
+  static const int latched = [] {
+    const char *e = std::getenv("GPU_MAX_HW_QUEUES");
+    const int q = e ? std::atoi(e) : 4;
+    return q > 0 ? q : 4;
+  }();
+  return latched;
+}
+// what of the handle the route reads (models = false: a call that ignores the per-problem models, qilqr_cost_trajectory)
+RouteInputs route_inputs(const qilqr_solver *s, bool models = true) {
+  return RouteInputs{s->symmetric, s->q_diag, layout_kind(s->layout), s->f32, s->integrator, s->limited, s->modeled && models,
+                     s->n_obstacles > 0, s->dev, s->num_cus, hw_queues()};
+}
+// the entry point a call comes through: a batch solve, qilqr_solve, a stand-alone pass, or qilqr_cost_trajectory (which ignores the models:
+// the cost does not depend on the model, and a call of any B takes the handle's own route)
+enum Entry { E_BATCH, E_SOLVE, E_PASS, E_COST };
+// The calls a handle refuses for what its extensions cannot do (the setters check the values they are given)
+int refuse(const qilqr_solver *s, long B, Entry call) {
+  if (call == E_BATCH && s->dev.persistent == 1) {
+    if (s->limited) return fail(QILQR_ERR_INVALID_ARG, "control limits: persistent = 1 (k_solve4) has no box form; take the rounds (persistent = 0)");
+    if (s->modeled)
+      return fail(QILQR_ERR_INVALID_ARG, "batch models: persistent = 1 (k_solve4) has one model for the batch; take the rounds (persistent = 0)");
+    if (s->n_obstacles > 0)
+      return fail(QILQR_ERR_INVALID_ARG, "obstacles: persistent = 1 (k_solve4) linearises without them; take the rounds (persistent = 0)");
+  }
+  if (call == E_SOLVE && s->modeled)
+    return fail(QILQR_ERR_INVALID_ARG, "batch models are set: qilqr_solve solves one problem with the handle's model; use qilqr_solve_batch, or "
+                                       "clear the models");
+  // per-problem models (qilqr_set_batch_models): problem b reads record b, so every computing call is over the rows they were set for
+  if (call != E_COST && s->modeled && B != s->models_B)
     return fail(QILQR_ERR_INVALID_ARG, "batch models were set for B = " + std::to_string(s->models_B) + " problems; this call has B = " +
                                            std::to_string(B) + " (set them again, or clear them, for another batch)");
   return QILQR_OK;
 }
-int begin_batch(qilqr_solver *s, long B, long n, const double *d_desired_batch) {
+// bind the desired trajectory (shared, or per problem: plain device array, re-tiled here), plan the call's route and reset the buffer
+// selectors
+int begin_batch(qilqr_solver *s, long B, long n, const double *d_desired_batch, Entry call) {
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
   if (!d_desired_batch && n > s->n_desired)
     return fail(QILQR_ERR_LENGTH_MISMATCH, "trajectory longer than desired trajectory");
-  int rc = check_batch_models(s, B);
+  int rc = refuse(s, B, call);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(s->device));
   rc = ensure_workspace(s, B, n);
@@ -378,7 +402,9 @@ int begin_batch(qilqr_solver *s, long B, long n, const double *d_desired_batch) 
   }
   s->total_B = B;
   s->live_hint = 0;  // (nothing known yet: launch_backward takes the batch)
-  s->st.layout.tiled = records_tiled(s, B, use_persistent(s, B)) ? 1 : 0;
+  const CallFacts facts{s->dev.sync_every, d_desired_batch != nullptr, s->st.cost_hist != nullptr, s->early_out != nullptr, 0.0 < s->params.max_iters};
+  s->route = plan_route(route_inputs(s, call != E_COST), B, facts);
+  s->st.layout.tiled = s->route.tiled ? 1 : 0;
   launch(s, K_OTHER, k_begin, dim3(cdiv(B, 256)), dim3(256), s->st, (int)B);
   return QILQR_OK;
 }
@@ -418,155 +444,80 @@ int download_tiled(qilqr_solver *s, double *h_plain, void *t0, void *t1, const i
   return QILQR_OK;
 }
 
-int launch_linearize(qilqr_solver *s, long B, long n, int which, int need_flag, int round = -1) {
+inline const ModelConsts<double> &consts_of(const qilqr_solver *s, double) { return s->consts; }
+inline const ModelConsts<float> &consts_of(const qilqr_solver *s, float) { return s->constsf; }
+// one k_linearize launch; the extension argument (per-problem models, obstacles, or both) rides behind the common ones
+template <typename S, int LK, int INTEG, bool TILED, typename... Ext>
+int lin(qilqr_solver *s, long B, long n, int which, int need_flag, int round, Ext... ext) {
   const dim3 grid(cdiv(2 * ((B + 63) / 64) * 64 * n, QILQR_LIN_BLOCK));  // dynamics half + cost half
-#define QILQR_LAUNCH_LIN(S, LK, TILED, CONSTS, DCONSTS) \
-  launch(s, K_LINEARIZE, (k_linearize<S, LK, 0, TILED>), grid, dim3(QILQR_LIN_BLOCK), CONSTS, DCONSTS, s->st, (int)B, (int)n, which, need_flag, round)
-#define QILQR_LAUNCH_LIN_RK4(LK) \
-  launch(s, K_LINEARIZE, (k_linearize<double, LK, 1, false>), grid, dim3(QILQR_LIN_BLOCK), s->consts, (const ModelConsts<double> *)s->d_consts, s->st, (int)B, (int)n, which, need_flag, round)
-  if (s->n_obstacles > 0) {  // the obstacle extension (fp64): the same record kinds and placements, the penalties added by the cost half
-    const Obstacles ob{s->d_obstacles, s->n_obstacles};
-    const int lk = (s->integrator == 0 && layout_kind(s->layout) == 2 && s->q_diag) ? 3 : layout_kind(s->layout);
-#define QILQR_LAUNCH_LIN_OBS(LK, INTEG, TILED, ...)                                                                                         \
-  launch(s, K_LINEARIZE, (k_linearize<double, LK, INTEG, TILED, __VA_ARGS__>), grid, dim3(QILQR_LIN_BLOCK), s->consts,                  \
-         (const ModelConsts<double> *)s->d_consts, s->st, (int)B, (int)n, which, need_flag, round, MOD_ARGS)
-    if (s->modeled) {  // ... beside the per-problem models (plain placement)
-      const ModelsObstacles mo{BatchModels{s->d_models}, ob};
-#define MOD_ARGS mo
-      switch (lk + (s->integrator == 1 ? 4 : 0)) {
-        case 0: QILQR_LAUNCH_LIN_OBS(0, 0, false, ModelsObstacles); break;
-        case 1: QILQR_LAUNCH_LIN_OBS(1, 0, false, ModelsObstacles); break;
-        case 2: QILQR_LAUNCH_LIN_OBS(2, 0, false, ModelsObstacles); break;
-        case 3: QILQR_LAUNCH_LIN_OBS(3, 0, false, ModelsObstacles); break;
-        case 4: QILQR_LAUNCH_LIN_OBS(0, 1, false, ModelsObstacles); break;
-        case 5: QILQR_LAUNCH_LIN_OBS(1, 1, false, ModelsObstacles); break;
-        default: QILQR_LAUNCH_LIN_OBS(2, 1, false, ModelsObstacles); break;
-      }
-#undef MOD_ARGS
-      return QILQR_OK;
-    }
-#define MOD_ARGS ob
-    // (the dense kind 0 is non-symmetric weights: the one-wavefront backward kernel, plain records -- records_tiled)
-    if (s->st.layout.tiled && (lk == 0 || s->integrator == 1)) return fail(QILQR_ERR_INVALID_ARG, "obstacles: no tiled records of this kind");
-    switch (lk + (s->integrator == 1 ? 4 : 0) + (s->st.layout.tiled ? 8 : 0)) {
-      case 0: QILQR_LAUNCH_LIN_OBS(0, 0, false, Obstacles); break;
-      case 1: QILQR_LAUNCH_LIN_OBS(1, 0, false, Obstacles); break;
-      case 2: QILQR_LAUNCH_LIN_OBS(2, 0, false, Obstacles); break;
-      case 3: QILQR_LAUNCH_LIN_OBS(3, 0, false, Obstacles); break;
-      case 4: QILQR_LAUNCH_LIN_OBS(0, 1, false, Obstacles); break;
-      case 5: QILQR_LAUNCH_LIN_OBS(1, 1, false, Obstacles); break;
-      case 6: QILQR_LAUNCH_LIN_OBS(2, 1, false, Obstacles); break;
-      case 9: QILQR_LAUNCH_LIN_OBS(1, 0, true, Obstacles); break;
-      case 10: QILQR_LAUNCH_LIN_OBS(2, 0, true, Obstacles); break;
-      default: QILQR_LAUNCH_LIN_OBS(3, 0, true, Obstacles); break;
-    }
-#undef MOD_ARGS
-#undef QILQR_LAUNCH_LIN_OBS
-    return QILQR_OK;
-  }
-  if (s->modeled) {  // the per-problem models extension: fp64, plain placement (the one-wavefront backward kernel reads the records)
-    const BatchModels bm{s->d_models};
-#define QILQR_LAUNCH_LIN_MOD(LK, INTEG)                                                                                                     \
-  launch(s, K_LINEARIZE, (k_linearize<double, LK, INTEG, false, BatchModels>), grid, dim3(QILQR_LIN_BLOCK), s->consts,                   \
-         (const ModelConsts<double> *)s->d_consts, s->st, (int)B, (int)n, which, need_flag, round, bm)
-    const int lk = (s->integrator == 0 && layout_kind(s->layout) == 2 && s->q_diag) ? 3 : layout_kind(s->layout);
-    switch (lk + (s->integrator == 1 ? 4 : 0)) {
-      case 0: QILQR_LAUNCH_LIN_MOD(0, 0); break;
-      case 1: QILQR_LAUNCH_LIN_MOD(1, 0); break;
-      case 2: QILQR_LAUNCH_LIN_MOD(2, 0); break;
-      case 3: QILQR_LAUNCH_LIN_MOD(3, 0); break;
-      case 4: QILQR_LAUNCH_LIN_MOD(0, 1); break;
-      case 5: QILQR_LAUNCH_LIN_MOD(1, 1); break;
-      default: QILQR_LAUNCH_LIN_MOD(2, 1); break;
-    }
-#undef QILQR_LAUNCH_LIN_MOD
-    return QILQR_OK;
-  }
-  if (s->integrator == 1) {  // the Runge-Kutta extension: dense M at the head of the record, fp64 only, plain placement
-    switch (layout_kind(s->layout)) {
-      case 0: QILQR_LAUNCH_LIN_RK4(0); break;
-      case 1: QILQR_LAUNCH_LIN_RK4(1); break;
-      default: QILQR_LAUNCH_LIN_RK4(2); break;
-    }
-    return QILQR_OK;
-  }
-  // (the placement of the records, s->st.layout.tiled, was chosen with the call's backward kernel: records_tiled)
-  if (layout_kind(s->layout) == 2 && s->q_diag && !s->f32) {
-    // diagonal Q: the record of kind 2, cheaper arithmetic, the same bits in fp64 (tests/test_gpu_parity.py).  (Not in the
-    // mixed mode: there the two instantiations differ in the last fp32 bit of a third of the knot costs -- the compiler
-    // contracts the single-precision expressions differently -- and "the same results whatever the weights' structure" is
-    // worth more than 1 % of k_linearize.)
-    if (s->st.layout.tiled) QILQR_LAUNCH_LIN(double, 3, true, s->consts, (const ModelConsts<double> *)s->d_consts);
-    else QILQR_LAUNCH_LIN(double, 3, false, s->consts, (const ModelConsts<double> *)s->d_consts);
-    return QILQR_OK;
-  }
-  switch (layout_kind(s->layout) + (s->f32 ? 3 : 0) + (s->st.layout.tiled ? 6 : 0)) {
-    case 0: QILQR_LAUNCH_LIN(double, 0, false, s->consts, (const ModelConsts<double> *)s->d_consts); break;
-    case 1: QILQR_LAUNCH_LIN(double, 1, false, s->consts, (const ModelConsts<double> *)s->d_consts); break;
-    case 2: QILQR_LAUNCH_LIN(double, 2, false, s->consts, (const ModelConsts<double> *)s->d_consts); break;
-    case 3: QILQR_LAUNCH_LIN(float, 0, false, s->constsf, (const ModelConsts<float> *)s->d_consts); break;
-    case 4: QILQR_LAUNCH_LIN(float, 1, false, s->constsf, (const ModelConsts<float> *)s->d_consts); break;
-    case 5: QILQR_LAUNCH_LIN(float, 2, false, s->constsf, (const ModelConsts<float> *)s->d_consts); break;
-    case 6: QILQR_LAUNCH_LIN(double, 0, true, s->consts, (const ModelConsts<double> *)s->d_consts); break;
-    case 7: QILQR_LAUNCH_LIN(double, 1, true, s->consts, (const ModelConsts<double> *)s->d_consts); break;
-    case 8: QILQR_LAUNCH_LIN(double, 2, true, s->consts, (const ModelConsts<double> *)s->d_consts); break;
-    case 9: QILQR_LAUNCH_LIN(float, 0, true, s->constsf, (const ModelConsts<float> *)s->d_consts); break;
-    case 10: QILQR_LAUNCH_LIN(float, 1, true, s->constsf, (const ModelConsts<float> *)s->d_consts); break;
-    default: QILQR_LAUNCH_LIN(float, 2, true, s->constsf, (const ModelConsts<float> *)s->d_consts); break;
-  }
-#undef QILQR_LAUNCH_LIN
-#undef QILQR_LAUNCH_LIN_RK4
+  launch(s, K_LINEARIZE, (k_linearize<S, LK, INTEG, TILED, Ext...>), grid, dim3(QILQR_LIN_BLOCK), consts_of(s, S()),
+         (const ModelConsts<S> *)s->d_consts, s->st, (int)B, (int)n, which, need_flag, round, ext...);
   return QILQR_OK;
 }
-// Which backward kernel a call with `load_B` trajectories in flight takes (symmetric weights), by how many trajectories share
-// the chip's 1024 SIMDs:
-//   up to 4096: k_backward4<.., FUSED>: four wavefronts that each carry the matrix AND the gradient recursion of a trajectory,
-//               and one loader wavefront, per four trajectories (the wavefronts are bound by latencies, the gradient's 40
-//               instructions ride along: +0.3 to +1.7 % of a whole solve against the form below, profiles/r03_ab_backward.txt)
-//   beyond:     k_backward4: four matrix wavefronts, ONE gradient wavefront and the loader per four trajectories, knot loop
-//               unrolled (four blocks per CU: the SIMDs are bound by what their wavefronts issue, and one gradient wavefront
-//               for four trajectories issues a quarter: 426k against 408k solves/s at 8192)
-// Until round 4 the one-wavefront kernel (k_backward<true>) took over above 8192 trajectories: a block per trajectory wastes
-// nothing on finished neighbours.  With the live trajectories compacted (k_compact_*) the blocks of four are full, and the
-// six-wavefront form is ahead at every size measured (profiles/r04_compaction.txt: 12288: 554k against 464k solves/s,
-// 16384: 593k / 512k, 65536: 654k / 587k); the one-wavefront kernel stays for force_general = 2.
-// k_backward2 (a matrix and a gradient wavefront per trajectory) was the choice below 512 trajectories in rounds 1 and 2; it
-// wins nowhere by more than 2 % and lives in the diagnostics build (force_general = 3 there).
-// The Runge-Kutta extension, the thrust limits, the per-problem models and non-symmetric weights take the one-wavefront kernel at every size.
-#ifndef QILQR_GFAC_MIN_LIVE
-#define QILQR_GFAC_MIN_LIVE 3072
-#endif
-constexpr long GFAC_MIN_LIVE = QILQR_GFAC_MIN_LIVE;  // running trajectories from which the gradient wavefront factors Q_uu (launch_backward)
-enum BackwardKind { BW_FOUR, BW_TWO, BW_ONE, BW_FUSED };
-BackwardKind backward_kind(const qilqr_solver *s, long load_B) {
-  if (s->integrator == 1 || !s->symmetric || s->limited || s->modeled) return BW_ONE;
-#ifdef QILQR_WITH_BACKWARD2
-  if (s->dev.force_general == 3) return BW_TWO;
-#endif
-  if (s->dev.force_general == 5 || (s->dev.force_general == 0 && load_B <= REGIME_B)) return BW_FUSED;
-  if (s->dev.force_general != 2) return BW_FOUR;
-  return BW_ONE;
-}
-// The knot records are placed for their reader (se3_math.h, rec_base): tiled for the kernels that stage them through LDS
-// (k_backward4, k_backward2, k_solve4), plain for the one-wavefront kernel.  Decided once per call, with the batch size
-// the kernel choice goes by.
-bool records_tiled(const qilqr_solver *s, long load_B, bool persistent) {
-  return persistent || backward_kind(s, load_B) != BW_ONE;
+constexpr int lin_key(int lk, int integ, bool tiled, bool f32, int ext) { return lk + 4 * integ + 8 * tiled + 16 * f32 + 32 * ext; }
+enum { LIN_PLAIN, LIN_MODELS, LIN_OBSTACLES, LIN_BOTH };
+int launch_linearize(qilqr_solver *s, long B, long n, int which, int need_flag, int round = -1) {
+  const Route &r = s->route;
+  const BatchModels bm{s->d_models};
+  const Obstacles ob{s->d_obstacles, s->n_obstacles};
+  const ModelsObstacles mo{bm, ob};
+  const int ext = (r.linearize_ext.models ? LIN_MODELS : LIN_PLAIN) | (r.linearize_ext.obstacles ? LIN_OBSTACLES : LIN_PLAIN);
+  // Every instantiation the routes take, and no other: the extensions are fp64 and plain-placed but for the obstacles' tiled records (the
+  // symmetric kinds), the Runge-Kutta records (INTEG = 1) are plain and have no diagonal kind.  (The placement of the records, s->st.layout.tiled,
+  // was chosen with the call's backward kernel: Route::tiled.)
+  switch (lin_key(r.lin_kind, r.integrator, s->st.layout.tiled != 0, r.f32, ext)) {
+    case lin_key(0, 0, false, false, LIN_BOTH): return lin<double, 0, 0, false>(s, B, n, which, need_flag, round, mo);
+    case lin_key(1, 0, false, false, LIN_BOTH): return lin<double, 1, 0, false>(s, B, n, which, need_flag, round, mo);
+    case lin_key(2, 0, false, false, LIN_BOTH): return lin<double, 2, 0, false>(s, B, n, which, need_flag, round, mo);
+    case lin_key(3, 0, false, false, LIN_BOTH): return lin<double, 3, 0, false>(s, B, n, which, need_flag, round, mo);
+    case lin_key(0, 1, false, false, LIN_BOTH): return lin<double, 0, 1, false>(s, B, n, which, need_flag, round, mo);
+    case lin_key(1, 1, false, false, LIN_BOTH): return lin<double, 1, 1, false>(s, B, n, which, need_flag, round, mo);
+    case lin_key(2, 1, false, false, LIN_BOTH): return lin<double, 2, 1, false>(s, B, n, which, need_flag, round, mo);
+    case lin_key(0, 0, false, false, LIN_OBSTACLES): return lin<double, 0, 0, false>(s, B, n, which, need_flag, round, ob);
+    case lin_key(1, 0, false, false, LIN_OBSTACLES): return lin<double, 1, 0, false>(s, B, n, which, need_flag, round, ob);
+    case lin_key(2, 0, false, false, LIN_OBSTACLES): return lin<double, 2, 0, false>(s, B, n, which, need_flag, round, ob);
+    case lin_key(3, 0, false, false, LIN_OBSTACLES): return lin<double, 3, 0, false>(s, B, n, which, need_flag, round, ob);
+    case lin_key(0, 1, false, false, LIN_OBSTACLES): return lin<double, 0, 1, false>(s, B, n, which, need_flag, round, ob);
+    case lin_key(1, 1, false, false, LIN_OBSTACLES): return lin<double, 1, 1, false>(s, B, n, which, need_flag, round, ob);
+    case lin_key(2, 1, false, false, LIN_OBSTACLES): return lin<double, 2, 1, false>(s, B, n, which, need_flag, round, ob);
+    case lin_key(1, 0, true, false, LIN_OBSTACLES): return lin<double, 1, 0, true>(s, B, n, which, need_flag, round, ob);
+    case lin_key(2, 0, true, false, LIN_OBSTACLES): return lin<double, 2, 0, true>(s, B, n, which, need_flag, round, ob);
+    case lin_key(3, 0, true, false, LIN_OBSTACLES): return lin<double, 3, 0, true>(s, B, n, which, need_flag, round, ob);
+    case lin_key(0, 0, false, false, LIN_MODELS): return lin<double, 0, 0, false>(s, B, n, which, need_flag, round, bm);
+    case lin_key(1, 0, false, false, LIN_MODELS): return lin<double, 1, 0, false>(s, B, n, which, need_flag, round, bm);
+    case lin_key(2, 0, false, false, LIN_MODELS): return lin<double, 2, 0, false>(s, B, n, which, need_flag, round, bm);
+    case lin_key(3, 0, false, false, LIN_MODELS): return lin<double, 3, 0, false>(s, B, n, which, need_flag, round, bm);
+    case lin_key(0, 1, false, false, LIN_MODELS): return lin<double, 0, 1, false>(s, B, n, which, need_flag, round, bm);
+    case lin_key(1, 1, false, false, LIN_MODELS): return lin<double, 1, 1, false>(s, B, n, which, need_flag, round, bm);
+    case lin_key(2, 1, false, false, LIN_MODELS): return lin<double, 2, 1, false>(s, B, n, which, need_flag, round, bm);
+    case lin_key(0, 1, false, false, LIN_PLAIN): return lin<double, 0, 1, false>(s, B, n, which, need_flag, round);
+    case lin_key(1, 1, false, false, LIN_PLAIN): return lin<double, 1, 1, false>(s, B, n, which, need_flag, round);
+    case lin_key(2, 1, false, false, LIN_PLAIN): return lin<double, 2, 1, false>(s, B, n, which, need_flag, round);
+    case lin_key(3, 0, true, false, LIN_PLAIN): return lin<double, 3, 0, true>(s, B, n, which, need_flag, round);
+    case lin_key(3, 0, false, false, LIN_PLAIN): return lin<double, 3, 0, false>(s, B, n, which, need_flag, round);
+    case lin_key(0, 0, false, false, LIN_PLAIN): return lin<double, 0, 0, false>(s, B, n, which, need_flag, round);
+    case lin_key(1, 0, false, false, LIN_PLAIN): return lin<double, 1, 0, false>(s, B, n, which, need_flag, round);
+    case lin_key(2, 0, false, false, LIN_PLAIN): return lin<double, 2, 0, false>(s, B, n, which, need_flag, round);
+    case lin_key(0, 0, false, true, LIN_PLAIN): return lin<float, 0, 0, false>(s, B, n, which, need_flag, round);
+    case lin_key(1, 0, false, true, LIN_PLAIN): return lin<float, 1, 0, false>(s, B, n, which, need_flag, round);
+    case lin_key(2, 0, false, true, LIN_PLAIN): return lin<float, 2, 0, false>(s, B, n, which, need_flag, round);
+    case lin_key(0, 0, true, false, LIN_PLAIN): return lin<double, 0, 0, true>(s, B, n, which, need_flag, round);
+    case lin_key(1, 0, true, false, LIN_PLAIN): return lin<double, 1, 0, true>(s, B, n, which, need_flag, round);
+    case lin_key(2, 0, true, false, LIN_PLAIN): return lin<double, 2, 0, true>(s, B, n, which, need_flag, round);
+    case lin_key(0, 0, true, true, LIN_PLAIN): return lin<float, 0, 0, true>(s, B, n, which, need_flag, round);
+    case lin_key(1, 0, true, true, LIN_PLAIN): return lin<float, 1, 0, true>(s, B, n, which, need_flag, round);
+    case lin_key(2, 0, true, true, LIN_PLAIN): return lin<float, 2, 0, true>(s, B, n, which, need_flag, round);
+  }
+  return fail(QILQR_ERR_INVALID_ARG, "k_linearize: no instantiation for this route");
 }
 int launch_backward(qilqr_solver *s, long B, long n, int force) {
 #define QILQR_LAUNCH_BWD(SYM, S)                                                                              \
   launch(s, K_BACKWARD, (k_backward<SYM, S>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, \
                      (int)B, (int)n, force)
-  const long load_B = std::max(B, s->total_B);
-  // (the records were linearised in the placement this choice reads: begin_batch sets st.layout.tiled from the same function;
-  // the one-wavefront kernel addresses its operands through rec_elem and reads either)
-  BackwardKind kind = s->st.layout.tiled ? backward_kind(s, load_B) : BW_ONE;
+  const Route &r = s->route;
   // `live` = the trajectories known to be running on the device in this call (every sub-batch stream's last count; the batch while nothing is known)
-  const long live = s->live_hint > 0 ? s->live_hint : load_B;
-  // Since round 6 the fused and the six-wavefront forms give the same bits, so a batch of up to 4096 trajectories takes the six-wavefront form
-  // (Q_uu factored by the gradient wavefront, four blocks per CU) for the launches in which most of it is still running -- every trajectory live,
-  // per launch: 4096: 248 against 293 us, 3072: 177 / 184, 2048: 123 / 127, 1024: 86 / 74 -- and the fused form from there on.
-  if (kind == BW_FUSED && s->dev.force_general == 0 && live >= GFAC_MIN_LIVE) kind = BW_FOUR;
+  const long live = s->live_hint > 0 ? s->live_hint : std::max(B, s->total_B);
+  const BackwardKind kind = backward_now(r, live);
   if (kind == BW_FUSED) {
     // four matrix-and-gradient wavefronts + one loader wavefront per four trajectories, no block barrier in the knot loop
     // (one register budget: the pipelined knot carries the previous knot's tail and does not fit 80 registers)
@@ -578,17 +529,7 @@ int launch_backward(qilqr_solver *s, long B, long n, int force) {
   } else if (kind == BW_FOUR) {
     // four matrix wavefronts + one gradient wavefront + one loader wavefront per four trajectories
     // (register budget by how many blocks the chip has to hold: see k_backward4)
-#ifdef QILQR_FORCE_MANY  // (experiment: the four-blocks-per-CU register budget and the unrolled knot loop at every size)
-    const bool many = true;
-#else
-    const bool many = load_B > REGIME_B;
-#endif
-    // Who factors Q_uu (round 6; the same bits either way, backward4_kernel.h): the gradient wavefront when the chip is saturated -- a SIMD
-    // is then bound by what its wavefronts issue, and one instruction stream factors four trajectories' Q_uu instead of four (a launch with
-    // every trajectory live, MI355X, N = 100: B = 65536 3807 -> 3515 us, 8192 509 -> 484) -- and the matrix wavefronts when a launch's
-    // wavefronts are alone on their SIMDs and its time is the chain of one knot's dependent instructions (B = 64: 75.3 against 85.3 us;
-    // level at 2048).
-    const bool gfac = s->dev.force_general == 7 || (s->dev.force_general != 8 && (many || s->dev.force_general == 0) && live >= GFAC_MIN_LIVE);
+    const bool many = r.many, gfac = gradient_factors(r, live);
     if (gfac && s->f32)
       launch(s, K_BACKWARD, (k_backward4<float, 6, false, false, true>), dim3(cdiv(B, 4)), dim3(384), s->consts, s->params, s->st, (int)B, (int)n, force);
     else if (gfac)
@@ -611,16 +552,16 @@ int launch_backward(qilqr_solver *s, long B, long n, int force) {
       launch(s, K_BACKWARD, k_backward2<double>, dim3((unsigned)B), dim3(128), s->consts, s->params, s->st, (int)B,
              (int)n, force);
 #endif
-  } else if (s->modeled) {  // the per-problem models extension (fp64): the constant rows of J_u from each problem's record
+  } else if (r.backward_ext.models) {  // the per-problem models extension (fp64): the constant rows of J_u from each problem's record
     const BatchModels bm{s->d_models};
-    if (s->limited)  // ... with the thrust limits: the box form
+    if (r.backward_ext.limits)  // ... with the thrust limits: the box form
       launch(s, K_BACKWARD, (k_backward_models<true, ControlLimits>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, (int)B,
              (int)n, force, bm, s->limits);
     else if (s->symmetric)
       launch(s, K_BACKWARD, (k_backward_models<true>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, (int)B, (int)n, force, bm);
     else
       launch(s, K_BACKWARD, (k_backward_models<false>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, (int)B, (int)n, force, bm);
-  } else if (s->limited) {  // the thrust-limit extension: the box form (symmetric weights, fp64: qilqr_set_control_limits)
+  } else if (r.backward_ext.limits) {  // the thrust-limit extension: the box form (symmetric weights, fp64: qilqr_set_control_limits)
     launch(s, K_BACKWARD, (k_backward<true, double, ControlLimits>), dim3((unsigned)B), dim3(64), s->consts, s->params, s->st, (int)B, (int)n,
            force, s->limits);
   } else if (s->symmetric) {
@@ -633,45 +574,34 @@ int launch_backward(qilqr_solver *s, long B, long n, int force) {
 #undef QILQR_LAUNCH_BWD
   return QILQR_OK;
 }
-#ifndef QILQR_ROLLOUT16_FROM
-#define QILQR_ROLLOUT16_FROM 16
-#endif
-constexpr long ROLLOUT16_FROM = QILQR_ROLLOUT16_FROM;
-// ordinal: which rollout of its solve this is for every trajectory that takes part (a running trajectory rolls out exactly once per round, so
-// the k-th rollout of ANY problem happens in round k of ANY call: a property of the problem, not of the batch); -1: the stand-alone entry points
+// ordinal: which rollout of its solve this is (rollout16_now); -1: the stand-alone entry points
 int launch_rollout(qilqr_solver *s, long B, long n, int need_flag, long ordinal = -1) {
-  // Which rollout kernel, by how many trajectories share the chip (qilqr_device_config.single_wave_rollout):
-  //   k_rollout16  sixteen lanes per trajectory, four trajectories per block: the shortest chain per trajectory and a
-  //                block on every CU from 1024 trajectories on; up to R16_MAX_B trajectories
-  //   k_rollout3   a lane per trajectory, three cooperating wavefronts per 64 trajectories: beyond
-  //   k_rollout    a lane per trajectory, one wavefront (the Runge-Kutta extension; forced).  It was the choice above 16384
-  //                trajectories until the live trajectories were compacted: with full wavefronts k_rollout3 is ahead there too
-  //                (65536: 698k against 655k solves/s, 16384: 596k / 543k, profiles/r04_compaction.txt)
-  const long load_B = std::max(B, s->total_B);
-  const int choice = s->dev.single_wave_rollout;
-  if (s->modeled) {  // the per-problem models extension (either integrator, with or without limits): the lane-per-trajectory kernel
+  // (which rollout kernel, by how many trajectories share the chip: route.h, RolloutRule)
+  const Route &r = s->route;
+  const ExtArgs &x = r.rollout_ext;
+  if (r.rollout == RO_LANE && x.models) {  // the per-problem models extension (either integrator, with or without limits)
     const BatchModels bm{s->d_models};
-    if (s->limited && s->integrator == 1)
+    if (x.limits && r.integrator == 1)
       launch(s, K_ROLLOUT, (k_rollout<double, 1, ControlLimits, BatchModels>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, s->limits, bm);
-    else if (s->limited)
+    else if (x.limits)
       launch(s, K_ROLLOUT, (k_rollout<double, 0, ControlLimits, BatchModels>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, s->limits, bm);
-    else if (s->integrator == 1)
+    else if (r.integrator == 1)
       launch(s, K_ROLLOUT, (k_rollout<double, 1, BatchModels>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, bm);
     else
       launch(s, K_ROLLOUT, (k_rollout<double, 0, BatchModels>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, bm);
-  } else if (s->limited) {  // the thrust-limit extension (either integrator): the lane-per-trajectory kernel, controls clamped
-    if (s->integrator == 1)
+  } else if (r.rollout == RO_LANE && x.limits) {  // the thrust-limit extension (either integrator): controls clamped
+    if (r.integrator == 1)
       launch(s, K_ROLLOUT, (k_rollout<double, 1, ControlLimits>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, s->limits);
     else
       launch(s, K_ROLLOUT, (k_rollout<double, 0, ControlLimits>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag, s->limits);
-  } else if (s->integrator == 1) {  // the Runge-Kutta extension: the lane-per-trajectory kernel only
+  } else if (r.rollout == RO_LANE && r.integrator == 1) {  // the Runge-Kutta extension: the lane-per-trajectory kernel only
     launch(s, K_ROLLOUT, (k_rollout<double, 1>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag);
-  } else if (choice == 1) {  // (a forced choice is honoured at every batch size; until round 4 also the choice above 16384)
+  } else if (r.rollout == RO_LANE) {  // (single_wave_rollout = 1: until round 4 also the choice above 16384)
     if (s->f32)
       launch(s, K_ROLLOUT, (k_rollout<float, 0>), dim3(cdiv(B, 64)), dim3(64), s->constsf, s->st, (int)B, (int)n, need_flag);
     else
       launch(s, K_ROLLOUT, (k_rollout<double, 0>), dim3(cdiv(B, 64)), dim3(64), s->consts, s->st, (int)B, (int)n, need_flag);
-  } else if (choice == 3 || (choice == 0 && load_B <= R16_MAX_B) || (choice == 0 && ordinal >= ROLLOUT16_FROM)) {
+  } else if (rollout16_now(r, ordinal)) {
     if (s->f32)
       launch(s, K_ROLLOUT, k_rollout16<float>, dim3(cdiv(B, 4)), dim3(192), s->consts, s->st, (int)B, (int)n, need_flag);
     else
@@ -684,28 +614,6 @@ int launch_rollout(qilqr_solver *s, long B, long n, int need_flag, long ordinal 
   }
   return QILQR_OK;
 }
-// k_backward_rollout (round_kernels.h): the backward pass and the rollout of a round in one launch, when every block of four
-// trajectories has a CU to itself (the rollout's register budget allows one block per CU) and the round's kernels are the
-// fused k_backward4 and k_rollout16 anyway.  qilqr_device_config.round_launch = 1 keeps them apart (A/B).
-// (the kernels of the round are the two the combined launch stands for: everything but the room on the chip)
-// (total_B / tiled: the call's batch in flight and its record placement -- the solver's own during a call, the caller's for qilqr_describe,
-// which asks about a batch without touching the handle's state)
-bool fuse_kinds(const qilqr_solver *s, long B, long total_B, bool tiled) {
-  const bool off = s->dev.round_launch == 1;  // (qilqr_device_config.round_launch: three launches per round, A/B)
-  const long load_B = std::max(B, total_B);
-  if (off || s->integrator != 0 || s->limited || s->modeled || !s->symmetric || !tiled) return false;
-  // (force_general = 8 with the combined launch: k_round with the six-wavefront backward pass in EVERY launch -- tests, A/B)
-  if (!(s->dev.force_general == 0 || s->dev.force_general == 5 || s->dev.force_general == 8)) return false;
-  if (s->dev.force_general != 8 && backward_kind(s, load_B) != BW_FUSED) return false;
-  if (s->dev.force_general == 8 && (s->dev.round_launch != 0 || s->f32 || s->n_obstacles > 0)) return false;  // (only k_round has the form: not k_backward_rollout)
-  if (!(s->dev.single_wave_rollout == 0 || s->dev.single_wave_rollout == 3) || load_B > R16_MAX_B) return false;
-  return true;
-}
-bool fuse_kinds(const qilqr_solver *s, long B) { return fuse_kinds(s, B, s->total_B, s->st.layout.tiled != 0); }
-bool fuse_backward_rollout(const qilqr_solver *s, long B, long total_B, bool tiled) {
-  return fuse_kinds(s, B, total_B, tiled) && cdiv(std::max(B, total_B), 4) <= (unsigned)s->num_cus;
-}
-bool fuse_backward_rollout(const qilqr_solver *s, long B) { return fuse_backward_rollout(s, B, s->total_B, s->st.layout.tiled != 0); }
 // Batch solves in flight on a device, over all the handles of the process.  The combined kernel takes a whole CU per block of
 // four trajectories (the rollout's register budget): alone on the chip that is +3 to +4 % of a solve, beside other solves'
 // kernels it is in their way -- three handles in flight: 306 000-311 000 solves/s with it, 340 000 without.  A solve that
@@ -722,16 +630,8 @@ struct InFlight {
   // (always: qilqr_device_config.fuse_in_flight = 1 keeps the combined launches beside other solves -- diagnostic)
   bool alone(bool always = false) const { return always || n.load(std::memory_order_relaxed) == 1; }
 };
-// k_round (round_kernels.h): the combined launch and the linearisation of its candidates in one.  fp64 storage only (the mixed mode keeps
-// the two launches).  The round's counts go into the counter set of its parity; the launch publishes the round before it.
-// A handle with obstacles keeps the two launches as well: k_round linearises with linearize_cost alone (the same bits as
-// k_backward_rollout + k_linearize, round_kernels.h), and only k_linearize adds the penalties.
-bool round_kernel_ok(const qilqr_solver *s) { return s->dev.round_launch == 0 && !s->f32 && s->n_obstacles == 0; }
-// rounds per launch of k_round where a launch may hold several (qilqr_device_config.rounds_per_launch = 1, 2 or 4: A/B; 0 = 4)
-int rounds_per_launch(const qilqr_solver *s) {
-  const int v = s->dev.rounds_per_launch;
-  return (v == 1 || v == 2) ? v : 4;
-}
+// k_round (round_kernels.h): the combined launch and the linearisation of its candidates in one (Route::round_kernel).  The round's counts go
+// into the counter set of its parity; the launch publishes the round before it.
 int launch_round(qilqr_solver *s, long B, long n, long round, bool publish_prev, int rounds, bool six = false) {
   const ModelConsts<double> *cp = (const ModelConsts<double> *)s->d_consts;
   if (rounds == 2) six = false;  // (the six-wavefront form is instantiated for launches of one and of four rounds)
@@ -741,32 +641,20 @@ int launch_round(qilqr_solver *s, long B, long n, long round, bool publish_prev,
   st.counters = base + (round & 1) * COUNT_WORDS;
   int *prev = base + ((round + 1) & 1) * COUNT_WORDS;
   const int prev_round = publish_prev ? (int)((round - 1) & 0x3fffffff) : -1;
-  const int lk = (s->q_diag && layout_kind(s->layout) == 2) ? 3 : (layout_kind(s->layout) == 2 ? 2 : 1);
-#define QILQR_LAUNCH_ROUND(LK, R) launch(s, K_BACKWARD, (k_round<LK, R>), grid, block, s->consts, cp, s->params, st, (int)B, (int)n, prev, prev_round)
-#define QILQR_LAUNCH_ROUND6(LK, R) launch(s, K_BACKWARD, (k_round<LK, R, true>), grid, block, s->consts, cp, s->params, st, (int)B, (int)n, prev, prev_round)
-  if (six && rounds == 4) {
-    if (lk == 3) QILQR_LAUNCH_ROUND6(3, 4);
-    else if (lk == 2) QILQR_LAUNCH_ROUND6(2, 4);
-    else QILQR_LAUNCH_ROUND6(1, 4);
-  } else if (six) {
-    if (lk == 3) QILQR_LAUNCH_ROUND6(3, 1);
-    else if (lk == 2) QILQR_LAUNCH_ROUND6(2, 1);
-    else QILQR_LAUNCH_ROUND6(1, 1);
-  } else if (rounds == 4) {
-    if (lk == 3) QILQR_LAUNCH_ROUND(3, 4);
-    else if (lk == 2) QILQR_LAUNCH_ROUND(2, 4);
-    else QILQR_LAUNCH_ROUND(1, 4);
-  } else if (rounds == 2) {
-    if (lk == 3) QILQR_LAUNCH_ROUND(3, 2);
-    else if (lk == 2) QILQR_LAUNCH_ROUND(2, 2);
-    else QILQR_LAUNCH_ROUND(1, 2);
-  } else {
-    if (lk == 3) QILQR_LAUNCH_ROUND(3, 1);
-    else if (lk == 2) QILQR_LAUNCH_ROUND(2, 1);
-    else QILQR_LAUNCH_ROUND(1, 1);
+  const int lk = std::max(s->route.lin_kind, 1);  // (the record kind of k_linearize: k_round takes the symmetric ones)
+#define QILQR_LAUNCH_ROUND(LK, R, SIX)                                                                                                          \
+  case LK * 16 + R * 2 + SIX:                                                                                                                     \
+    launch(s, K_BACKWARD, (k_round<LK, R, SIX>), grid, block, s->consts, cp, s->params, st, (int)B, (int)n, prev, prev_round);                    \
+    break
+  switch (lk * 16 + rounds * 2 + (six ? 1 : 0)) {
+    QILQR_LAUNCH_ROUND(3, 4, true); QILQR_LAUNCH_ROUND(2, 4, true); QILQR_LAUNCH_ROUND(1, 4, true);
+    QILQR_LAUNCH_ROUND(3, 1, true); QILQR_LAUNCH_ROUND(2, 1, true); QILQR_LAUNCH_ROUND(1, 1, true);
+    QILQR_LAUNCH_ROUND(3, 4, false); QILQR_LAUNCH_ROUND(2, 4, false); QILQR_LAUNCH_ROUND(1, 4, false);
+    QILQR_LAUNCH_ROUND(3, 2, false); QILQR_LAUNCH_ROUND(2, 2, false); QILQR_LAUNCH_ROUND(1, 2, false);
+    QILQR_LAUNCH_ROUND(3, 1, false); QILQR_LAUNCH_ROUND(2, 1, false); QILQR_LAUNCH_ROUND(1, 1, false);
+    default: return fail(QILQR_ERR_INVALID_ARG, "k_round: no instantiation for this launch");
   }
 #undef QILQR_LAUNCH_ROUND
-#undef QILQR_LAUNCH_ROUND6
   return QILQR_OK;
 }
 int launch_backward_rollout(qilqr_solver *s, long B, long n) {
@@ -782,18 +670,7 @@ int launch_accept(qilqr_solver *s, long B, long n, int ls_only) {
   return QILQR_OK;
 }
 
-// ---- compaction of the live trajectories (bookkeeping_kernels.h, k_compact_plan): between a round's backward pass and its rollout.
-// Worth its two launches while the live trajectories fill more blocks than the device runs side by side; below
-// COMPACT_STOP running trajectories every kernel of a round is a lone dependent chain whatever the slots are.
-#ifndef QILQR_COMPACT_STOP
-#define QILQR_COMPACT_STOP 512
-#endif
-constexpr unsigned COMPACT_STOP = QILQR_COMPACT_STOP;
-// Automatic (qilqr_device_config.compaction = 0): whenever the round's backward pass is a k_backward4 (blocks of four trajectories)
-// and not part of the combined launch of B <= 1024 -- measured, one configuration per process (profiles/r04_compaction.txt): 1280:
-// +5 %, 2048: +5.5 %, 3072: +13 %, 4096: +8 %, 8192: +6 %; with the one-wavefront backward kernel (general weights, the Runge-Kutta
-// extension, force_general = 2), whose blocks hold one trajectory, it gains nothing (12288-32768: -2 to +1 %) and stays off.
-inline unsigned compact_stop(const qilqr_solver *s) { return s->dev.compaction == 1 ? 0u : COMPACT_STOP; }
+// ---- compaction of the live trajectories (route.h: COMPACT_STOP, Route::compact, tail_fuse)
 // Behind a round's compaction every running trajectory sits in a slot below the count of running trajectories, and the last count
 // the host has read is an upper bound of that (counts only fall): the kernels that follow are launched over that many slots instead
 // of the whole batch (in its tail a batch of 65536 otherwise pays 53 us per k_linearize launch for 100 000 blocks that find nothing
@@ -813,43 +690,23 @@ int launch_compact(qilqr_solver *s, long B, long n) {
   return QILQR_OK;
 }
 
-// A batch of 1025 ... 4096 trajectories runs the same two kernels apart, with the compaction between them; once the running
-// trajectories fit the combined launch -- `slots` of them for this (sub-)batch: a block of four per CU over all the sub-batches --
-// the compaction has nothing left to give and the rounds change over to the one launch.
-// Round 6: a batch BEYOND 4096 does the same from the round in which its rollouts are k_rollout16's anyway (launch_rollout: the 17th, or
-// every round with single_wave_rollout = 3) -- the backward pass is one arithmetic in every form, so the combined launch's fused form gives
-// the bits of the six-wavefront launches it replaces, and a problem's bits stay independent of its batch.
-struct TailFuse {
-  bool kinds = false;  // the round's kernels are the fused k_backward4 and k_rollout16 (or, from round `from` on, stand for the same bits)
-  long slots = 0;      // slots in use at or below which this (sub-)batch's rounds are one launch
-  unsigned stop = 0;   // the compaction runs while more trajectories than this are running
-  long from = 0;       // first round in which the changeover may happen
-};
-#ifndef QILQR_LATE_TAIL
-#define QILQR_LATE_TAIL 1  // (0: batches beyond 4096 keep three launches per round to the end -- A/B)
-#endif
-bool late_tail_kinds(const qilqr_solver *s, long B, long total_B, bool tiled, long *from) {
-  const long load_B = std::max(B, total_B);
-  if (!QILQR_LATE_TAIL || s->dev.round_launch == 1 || s->integrator != 0 || s->limited || s->modeled || !s->symmetric || !tiled) return false;
-  if (s->dev.force_general != 0 || load_B <= R16_MAX_B || backward_kind(s, load_B) != BW_FOUR) return false;
-  if (s->dev.single_wave_rollout == 0) *from = ROLLOUT16_FROM;
-  else if (s->dev.single_wave_rollout == 3) *from = 0;
-  else return false;
-  return true;
-}
-TailFuse tail_fuse(const qilqr_solver *s, long B, int nparts) {
-  TailFuse t;
-  t.stop = compact_stop(s);
-  if (!s->compact || s->dev.compaction == 1) return t;  // (forced: the compaction runs to the last trajectory)
-  t.kinds = fuse_kinds(s, B) || late_tail_kinds(s, B, s->total_B, s->st.layout.tiled != 0, &t.from);
-  if (t.kinds) {
-    // (a block of four per CU over the sub-batches of ONE stream, two per CU over two streams', three over three and more: measured once
-    // the tail ran on k_round -- profiles/r06_ab.txt section 14: B = 4096 + 1 %, 8192 + 2-3 %, 16384 + 1.5 %; a single stream at two blocks
-    // per CU loses 17 % at B = 2048, whose whole solve would then be the tail)
-    t.slots = std::max<long>(64, std::min(nparts, 3) * 4L * s->num_cus / nparts / 64 * 64);
-    t.stop = std::max<unsigned>(t.stop, (unsigned)t.slots);
+// The count of running trajectories that the launches of round `old` hand to the host (the word's high half is the round's tag): a bounded
+// wait on `stream`, which never spins on a dead stream -- a drained or failed stream without the tag is an error.
+int wait_for_count(const unsigned long long *word, hipStream_t stream, long old, unsigned long long *v) {
+  const unsigned tag = (unsigned)((old & 0x3fffffff) + 1);
+  for (long spins = 0;; ++spins) {
+    *v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    if ((unsigned)(*v >> 32) == tag) return QILQR_OK;
+    if ((spins & 1023) == 1023) {
+      const hipError_t q = hipStreamQuery(stream);
+      if (q != hipErrorNotReady) {
+        *v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+        if ((unsigned)(*v >> 32) == tag) return QILQR_OK;
+        return fail(QILQR_ERR_HIP, std::string("a round never reported its active count: ") + hipGetErrorString(q));
+      }
+    }
+    __builtin_ia32_pause();
   }
-  return t;
 }
 
 int read_active(qilqr_solver *s, int *n_active) {
@@ -1003,8 +860,8 @@ int run_solve(qilqr_solver *s, long B, long n, int sync_every, F on_round, bool 
     };
     for (int k = 0; k < 8; ++k) s->h_active[k] = 0;
     const InFlight in_flight(s->device);
-    const bool can_fuse = fuse_backward_rollout(s, B) && !s->compact;  // (compaction works between the two halves)
-    const TailFuse tf = tail_fuse(s, B, 1);
+    const bool can_fuse = s->route.combined && !s->compact;  // (compaction works between the two halves)
+    const TailFuse tf = tail_fuse(s->route, s->compact, 1);
     if (s->compact) s->plan_heads.push_back(0);
     unsigned seen_active = (unsigned)B;  // the last count the host has read (the count only falls)
     long used = B;                       // slots the round's kernels are launched over (slots_in_use)
@@ -1024,16 +881,13 @@ int run_solve(qilqr_solver *s, long B, long n, int sync_every, F on_round, bool 
       // (until round 6 k_round linearised a block's candidates AFTER the rollout, 2.5 times slower than k_linearize with four candidates per
       // block and idle CUs beside it, and B = 64 ... 512 took k_backward_rollout + k_linearize in their first rounds; with the linearisation
       // behind the rollout -- round_follow -- k_round is ahead at every size: B = 64 + 2.1 %, 128 + 2.3 %, 256 + 3 %, 512 + 3.6 %)
-      if (fuse_now && round_kernel_ok(s)) {
+      if (fuse_now && s->route.round_kernel) {
         // several rounds per launch where the rounds are this kernel for the rest of the solve (no compaction any more, whose
         // thresholds go by the count) and the caller does not look at a solve round by round (the single solve's debug capture)
-        const int rounds = ((can_fuse || tail_started) && double_ok) ? rounds_per_launch(s) : 1;
-        // the backward pass's form by how many trajectories a block holds on average (the same bits: round_kernels.h)
-        // (and only in launches of several rounds: with one round per launch the 384-thread form measured slower)
-        const bool six = s->dev.force_general == 8 || (s->dev.force_general == 0 && rounds > 1 && 2L * (long)seen_active <= cdiv(used, 4) * 4L);
-        if ((rc = launch_round(s, used, n, round, pending_publish, rounds, six))) return rc;
+        const RoundForm f = round_form(s->route, (can_fuse || tail_started) && double_ok, /*forced=*/true, seen_active, used);
+        if ((rc = launch_round(s, used, n, round, pending_publish, f.rounds, f.six))) return rc;
         s->round_captured = true;
-        launched_rounds[round & 7] = rounds;
+        launched_rounds[round & 7] = f.rounds;
         pending_publish = true;
         two_sets = true;
         if ((rc = on_round())) return rc;
@@ -1066,22 +920,8 @@ int run_solve(qilqr_solver *s, long B, long n, int sync_every, F on_round, bool 
       // instead of eight -- measured no different: 4.71-4.73 ms either way)
       if (round >= lag) {
         const long old = round - lag;
-        const unsigned tag = (unsigned)((old & 0x3fffffff) + 1);
         unsigned long long v;
-        for (long spins = 0;; ++spins) {
-          v = __atomic_load_n(&s->h_active[old & 7], __ATOMIC_ACQUIRE);
-          if ((unsigned)(v >> 32) == tag) break;
-          if ((spins & 1023) == 1023) {
-            // never spin on a dead stream: a drained or failed stream without the tag is an error
-            const hipError_t q = hipStreamQuery(s->stream);
-            if (q != hipErrorNotReady) {
-              v = __atomic_load_n(&s->h_active[old & 7], __ATOMIC_ACQUIRE);
-              if ((unsigned)(v >> 32) == tag) break;
-              return fail(QILQR_ERR_HIP, std::string("a round never reported its active count: ") + hipGetErrorString(q));
-            }
-          }
-          __builtin_ia32_pause();
-        }
+        if ((rc = wait_for_count(&s->h_active[old & 7], s->stream, old, &v))) return rc;
         if ((unsigned)v == 0) break;
         // a launch of several rounds reports the SUM of their counts; counts only fall, so the mean over the launch's rounds is an upper
         // bound of the last round's -- of the count now
@@ -1168,33 +1008,6 @@ struct PartScope {
     s->stream = stream0;
   }
 };
-// hardware queues HIP multiplexes this process's streams onto: GPU_MAX_HW_QUEUES as the runtime read it at start-up (default 4)
-// Latched at the first qilqr_create_sized of the process, which calls it (the runtime reads the variable once, when it starts: a value
-// put into the environment later -- os.environ after the first GPU call -- changes nothing in the runtime and must change nothing here)
-int hw_queues() {
-  static const int latched = [] {
-    const char *e = std::getenv("GPU_MAX_HW_QUEUES");
-    const int q = e ? std::atoi(e) : 4;
-    return q > 0 ? q : 4;
-  }();
-  return latched;
-}
-int auto_parts(const qilqr_solver *s, long B) {
-  const long tiles = (B + 63) / 64;
-  // Measured (MI355X, N = 100): up to a few thousand trajectories every kernel is latency-bound and sharing
-  // SIMDs with another part's kernels only slows both (B = 1024, round 3: 194k solves/s on one stream, 168k on two,
-  // 153k on four); from 4096 on two parts gain 4-5%.  Between 4096 and 16384 FOUR parts are better still when
-  // every part's stream has a hardware queue of its own -- GPU_MAX_HW_QUEUES=8 in the environment before the runtime
-  // starts: 5120: 366k against 356k solves/s, 6144: 403k / 377k, 7168: 437k / 406k,
-  // 8192: 461k / 429k, 10240: 441k / 424k, 12288: 472k / 460k; level at 4096, 16384 and 65536; with HIP's default four queues
-  // the parts collide with each other and with the caller's streams and two are the safer choice.
-  // Round 4 (compaction, k_backward4 and k_rollout3 at every size beyond 4096): four parts are ahead at 16384 and 65536 as well
-  // (596k against 591k, 698k against 686k).
-  int want = s->dev.streams > 0 ? s->dev.streams : (B >= REGIME_B ? ((B > REGIME_B && hw_queues() >= 8) ? 4 : 2) : 1);
-  if (want > qilqr_solver::MAX_PARTS) want = qilqr_solver::MAX_PARTS;
-  while (want > 1 && tiles < 2 * want) --want;  // at least two tiles per part
-  return want;
-}
 // streams and completion events of the first nparts sub-batches, created on first use
 int ensure_parts(qilqr_solver *s, int nparts) {
   for (int k = 0; k < nparts; ++k) {
@@ -1240,7 +1053,7 @@ int run_solve_parts(qilqr_solver *s, long B, long n, int nparts) {
     const long max_rounds = (long)std::fmin(bound, 2e9);
     const int lag = std::max(1, std::min(s->dev.sync_every, 6));
     const InFlight in_flight(s->device);
-    const TailFuse tf = tail_fuse(s, B, nparts);
+    const TailFuse tf = tail_fuse(s->route, s->compact, nparts);
     for (long round = 0; round < max_rounds && remaining > 0; ++round) {
       long live_all = 0;  // (every part's last count: what shares the chip with this part's kernels)
       for (auto &part : parts) live_all += part.done ? 0 : (long)part.seen_active;
@@ -1257,11 +1070,10 @@ int run_solve_parts(qilqr_solver *s, long B, long n, int nparts) {
         if (part.tail && (part.round_kernel || in_flight.alone(s->dev.fuse_in_flight == 1))) {
           // as in run_solve: k_round, four rounds per launch (fp64; the mixed mode keeps the combined launch and k_linearize).  One way only,
           // so the round before the first k_round has been published by its own k_linearize and every later one by the k_round behind it.
-          if (round_kernel_ok(s) && QILQR_LATE_TAIL) {
-            const int rounds = rounds_per_launch(s);
-            const bool six = rounds > 1 && 2L * (long)part.seen_active <= cdiv(part.used, 4) * 4L;
-            if ((rc = launch_round(s, part.used, n, round, part.round_kernel, rounds, six))) return rc;
-            part.launched_rounds[round & 7] = (unsigned)rounds;
+          if (s->route.round_kernel && QILQR_LATE_TAIL) {
+            const RoundForm f = round_form(s->route, /*several=*/true, /*forced=*/false, part.seen_active, part.used);
+            if ((rc = launch_round(s, part.used, n, round, part.round_kernel, f.rounds, f.six))) return rc;
+            part.launched_rounds[round & 7] = (unsigned)f.rounds;
             part.round_kernel = true;
             continue;
           }
@@ -1279,23 +1091,10 @@ int run_solve_parts(qilqr_solver *s, long B, long n, int nparts) {
       }
       if (round < lag) continue;
       const long old = round - lag;
-      const unsigned tag = (unsigned)((old & 0x3fffffff) + 1);
       for (auto &part : parts) {
         if (part.done) continue;
         unsigned long long v;
-        for (long spins = 0;; ++spins) {
-          v = __atomic_load_n(&part.h_active[old & 7], __ATOMIC_ACQUIRE);
-          if ((unsigned)(v >> 32) == tag) break;
-          if ((spins & 1023) == 1023) {
-            const hipError_t q = hipStreamQuery(part.stream);
-            if (q != hipErrorNotReady) {
-              v = __atomic_load_n(&part.h_active[old & 7], __ATOMIC_ACQUIRE);
-              if ((unsigned)(v >> 32) == tag) break;
-              return fail(QILQR_ERR_HIP, std::string("a round never reported its active count: ") + hipGetErrorString(q));
-            }
-          }
-          __builtin_ia32_pause();
-        }
+        if ((rc = wait_for_count(&part.h_active[old & 7], part.stream, old, &v))) return rc;
         // (a launch of several rounds reports the sum of their counts: the mean bounds the last round's)
         part.seen_active = ((unsigned)v + part.launched_rounds[old & 7] - 1) / part.launched_rounds[old & 7];
         if ((unsigned)v == 0) {
@@ -1340,31 +1139,14 @@ int check_quaternions(const double *traj, long count, const char *what) {
   return QILQR_OK;
 }
 
-// The persistent solve (solve4.h): every trajectory from its first linearisation to its exit status in ONE launch.
-// Requirements: symmetric weights (the matrix-core recursion of k_backward4), no per-round host visibility (debug capture
-// of trajectories uses the rounds).  qilqr_device_config.persistent: 0 = by measurement, 1 = always, 2 = never.
-// By measurement (profiles/microbench/persistent_sweep.py, MI355X, N = 100, device-resident, ms per batch solve) the rounds are
-// level or ahead at every batch size but one -- 256: 4.15 vs 4.45, 1024: 5.63 vs 5.74, 1536: 7.52 vs 7.21, 2048: 8.1 vs 9.5,
-// 8192: 22.0 vs 27.6: both paths are bound by (iterations of the slowest trajectory) x (latency of one iteration), and inside
-// k_solve4 the forward phase ends one linearisation task (~11 us) after the rollout while its step waves run beside three
-// linearising wavefronts.
-// So 0 selects the rounds; the persistent solve stays selectable and tested.
-bool use_persistent(const qilqr_solver *s, long B) {
-  (void)B;
-#ifdef QILQR_WITH_SOLVE4
-  return s->symmetric && s->dev.persistent == 1 && s->integrator == 0 && !s->limited && !s->modeled && s->n_obstacles == 0;
-#else
-  (void)s;
-  return false;  // k_solve4 is in the diagnostics build (qilqr_create refuses persistent = 1 here)
-#endif
-}
+// The persistent solve (solve4.h; Route::persistent): every trajectory from its first linearisation to its exit status in ONE launch.
 #ifdef QILQR_WITH_SOLVE4
 int launch_solve4(qilqr_solver *s, long B, long n) {
   const unsigned groups = cdiv(B, 4);
   const unsigned grid = std::min<unsigned>(groups, (unsigned)s->num_cus);  // one block per CU (256 VGPRs, 105 KB of LDS); the rest queue
 #define QILQR_LAUNCH_S4(S, LK) \
   launch(s, K_SOLVE, k_solve4<S, LK>, dim3(grid), dim3(S4_THREADS), s->consts, (const ModelConsts<S> *)s->d_consts, s->params, s->st, (int)B, (int)n, 0u)
-  switch (layout_kind(s->layout) + (s->f32 ? 3 : 0)) {
+  switch (layout_kind(s->layout) + (s->route.f32 ? 3 : 0)) {
     case 0: QILQR_LAUNCH_S4(double, 0); break;
     case 1: QILQR_LAUNCH_S4(double, 1); break;
     case 2: QILQR_LAUNCH_S4(double, 2); break;
@@ -1385,23 +1167,13 @@ int solve_batch_device_impl(qilqr_solver *s, const double *d_init, const double 
                             double *d_out_traj, double *d_out_cost, int32_t *d_out_status, int32_t *d_out_iters,
                             int32_t *d_out_n_bwd, int32_t *d_out_n_fwd, bool drain) {
   if (!s || !d_init) return fail(QILQR_ERR_INVALID_ARG, "null argument");
-  if (s->limited && s->dev.persistent == 1)
-    return fail(QILQR_ERR_INVALID_ARG, "control limits: persistent = 1 (k_solve4) has no box form; take the rounds (persistent = 0)");
-  if (s->modeled && s->dev.persistent == 1)
-    return fail(QILQR_ERR_INVALID_ARG, "batch models: persistent = 1 (k_solve4) has one model for the batch; take the rounds (persistent = 0)");
-  if (s->n_obstacles > 0 && s->dev.persistent == 1)
-    return fail(QILQR_ERR_INVALID_ARG, "obstacles: persistent = 1 (k_solve4) linearises without them; take the rounds (persistent = 0)");
   const RoctxRange range(s, "batch solve, trajectories:", (long)B);
-  int rc = begin_batch(s, B, n, d_desired_batch);
+  int rc = begin_batch(s, B, n, d_desired_batch, E_BATCH);
   if (rc) return rc;
-  const bool persistent = use_persistent(s, B);
+  const bool persistent = s->route.persistent;
   if ((rc = to_tiled(s, d_init, s->st.traj[0], B, n, 18, persistent ? s->st.counters : nullptr))) return rc;
-  const int nparts = (s->dev.sync_every > 1) ? auto_parts(s, B) : 1;
-  // compaction: free-running rounds only (the host never waits for a plan), not beside the copy-back under the tail (it gathers by
-  // slot), the per-iteration cost history (rows by slot), per-problem desired trajectories or per-problem models (they would have to move along)
-  s->compact = s->dev.compaction >= 0 && s->dev.sync_every > 1 && !persistent && !s->st.cost_hist && !s->st.desired_tiled && !s->early_out && !s->modeled &&
-               0.0 < s->params.max_iters &&
-               (s->dev.compaction == 1 || (!fuse_backward_rollout(s, B) && backward_kind(s, B) != BW_ONE && s->st.layout.tiled));
+  const int nparts = s->route.parts;
+  s->compact = s->route.compact;
   s->compact_out = CompactOut{d_out_traj, d_out_cost, d_out_status, d_out_iters, d_out_n_bwd, d_out_n_fwd};
   s->plan_heads.clear();
   struct CompactScope {  // (every return below leaves the flag off for the other entry points)
@@ -1461,7 +1233,7 @@ int solve_batch_staged(qilqr_solver *s, const double *init, const double *desire
   if (!desired_batch && n > s->n_desired)
     return fail(QILQR_ERR_LENGTH_MISMATCH, "trajectory longer than desired trajectory");
   int rc;
-  if ((rc = check_batch_models(s, B))) return rc;  // (before anything is enqueued)
+  if ((rc = refuse(s, B, E_BATCH))) return rc;  // (before anything is enqueued)
   HIP_TRY(hipSetDevice(s->device));
   const size_t cnt = 18 * (size_t)B * n, tb = sizeof(double) * cnt;
   auto grow = [&](auto **p, size_t *cap, size_t want, size_t elem) -> hipError_t {
@@ -1788,7 +1560,7 @@ int qilqr_set_control_limits(qilqr_solver *s, const double *lo, const double *hi
   }
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  // (nothing of the workspace depends on the limits: the record placement is chosen per call, begin_batch -> records_tiled)
+  // (nothing of the workspace depends on the limits: the record placement is chosen per call, begin_batch -> Route::tiled)
   s->limited = lo != nullptr;
   if (lo)
     for (int a = 0; a < 4; ++a) {
@@ -1815,7 +1587,7 @@ int qilqr_set_batch_models(qilqr_solver *s, const qilqr_model *models, int32_t B
   }
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  // (nothing of the workspace depends on the models: the record placement is chosen per call, begin_batch -> records_tiled)
+  // (nothing of the workspace depends on the models: the record placement is chosen per call, begin_batch -> Route::tiled)
   s->modeled = false;
   s->models_B = 0;
   if (s->d_models) (void)hipFree(s->d_models);
@@ -1926,8 +1698,9 @@ int qilqr_solve_batch(qilqr_solver *s, const double *init, const double *desired
   EarlyOut eo{out_traj, out_cost, out_status, out_iters, out_n_bwd, out_n_fwd};
   LateLayout late{};
   eo.layout = &late;
-  const bool early = out_traj && B >= 256 && (size_t)B * n * 144 >= ((size_t)2 << 20) && s->dev.sync_every > 1 && auto_parts(s, B) == 1 &&
-                     !use_persistent(s, B) && 0.0 < s->params.max_iters && pinned_or_null(out_traj) && pinned_or_null(out_cost) &&
+  const Route route = plan_route(route_inputs(s), B, CallFacts{s->dev.sync_every});
+  const bool early = out_traj && B >= 256 && (size_t)B * n * 144 >= ((size_t)2 << 20) && s->dev.sync_every > 1 && route.parts == 1 &&
+                     !route.persistent && 0.0 < s->params.max_iters && pinned_or_null(out_traj) && pinned_or_null(out_cost) &&
                      pinned_or_null(out_status) && pinned_or_null(out_iters) && pinned_or_null(out_n_bwd) && pinned_or_null(out_n_fwd);
   if (early) {
     eo.threshold = (unsigned)(B / 8);
@@ -2016,12 +1789,9 @@ int qilqr_solve(qilqr_solver *s, const double *init, int32_t n, double *out_traj
                 int32_t debug_cap, int32_t *n_debug) {
   if (!s || !init || !out_traj) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   if (n <= 0) return fail(QILQR_ERR_INVALID_ARG, "empty trajectory");
-  if (s->modeled)
-    return fail(QILQR_ERR_INVALID_ARG, "batch models are set: qilqr_solve solves one problem with the handle's model; use qilqr_solve_batch, or "
-                                       "clear the models");
   int rc;
   if ((rc = check_quaternions(init, n, "initial trajectory"))) return rc;
-  if ((rc = begin_batch(s, 1, n, nullptr))) return rc;
+  if ((rc = begin_batch(s, 1, n, nullptr, E_SOLVE))) return rc;
   if ((rc = upload_tiled(s, init, s->st.traj[0], 1, n, 18))) return rc;
   const bool want_debug = s->options.populate_debug && debug_cap > 0 && (debug_cost || debug_trajs);
   if (want_debug) {
@@ -2090,14 +1860,7 @@ int qilqr_solve(qilqr_solver *s, const double *init, int32_t n, double *out_traj
 
 int qilqr_cost_trajectory(qilqr_solver *s, const double *traj, int32_t B, int32_t n, double *cost) {
   if (!s || !traj || !cost) return fail(QILQR_ERR_INVALID_ARG, "null argument");
-  // the cost does not depend on the model: with per-problem models set, this call (of any B) takes the handle's own route
-  struct ModelsOff {
-    qilqr_solver *s;
-    bool was;
-    ~ModelsOff() { s->modeled = was; }
-  } models_off{s, s->modeled};
-  s->modeled = false;
-  int rc = begin_batch(s, B, n, nullptr);
+  int rc = begin_batch(s, B, n, nullptr, E_COST);
   if (rc) return rc;
   if ((rc = upload_tiled(s, traj, s->st.traj[0], B, n, 18))) return rc;
   if ((rc = launch_linearize(s, B, n, 0, 0))) return rc;
@@ -2110,7 +1873,7 @@ int qilqr_cost_trajectory(qilqr_solver *s, const double *traj, int32_t B, int32_
 
 int qilqr_backwards_pass(qilqr_solver *s, const double *traj, int32_t B, int32_t n, double *gains, double *terms) {
   if (!s || !traj || !gains || !terms) return fail(QILQR_ERR_INVALID_ARG, "null argument");
-  int rc = begin_batch(s, B, n, nullptr);
+  int rc = begin_batch(s, B, n, nullptr, E_PASS);
   if (rc) return rc;
   if ((rc = upload_tiled(s, traj, s->st.traj[0], B, n, 18))) return rc;
   if ((rc = launch_linearize(s, B, n, 0, 0))) return rc;
@@ -2126,7 +1889,7 @@ int qilqr_backwards_pass(qilqr_solver *s, const double *traj, int32_t B, int32_t
 int qilqr_forward_sim(qilqr_solver *s, const double *traj, const double *gains, const double *alpha, int32_t B,
                       int32_t n, double *out_traj) {
   if (!s || !traj || !gains || !alpha || !out_traj) return fail(QILQR_ERR_INVALID_ARG, "null argument");
-  int rc = begin_batch(s, B, n, nullptr);
+  int rc = begin_batch(s, B, n, nullptr, E_PASS);
   if (rc) return rc;
   if ((rc = upload_tiled(s, traj, s->st.traj[0], B, n, 18))) return rc;
   if ((rc = upload_tiled(s, gains, s->st.gains, B, n, 52))) return rc;
@@ -2142,7 +1905,7 @@ int qilqr_line_search(qilqr_solver *s, const double *traj, const double *cost, c
                       const double *terms, int32_t B, int32_t n, double *out_traj, double *out_cost,
                       double *out_step, int32_t *out_status) {
   if (!s || !traj || !cost || !gains || !terms) return fail(QILQR_ERR_INVALID_ARG, "null argument");
-  int rc = begin_batch(s, B, n, nullptr);
+  int rc = begin_batch(s, B, n, nullptr, E_PASS);
   if (rc) return rc;
   struct Scratch {  // freed on every return path
     double *cost = nullptr, *terms = nullptr;
@@ -2761,11 +2524,12 @@ int qilqr_solve_batch_sharded_device(qilqr_sharded *h, const double *init, const
 // reference's own forms and the symmetric-weight kernels is made by whether Q and R are bit-exactly symmetric, and was silent).
 int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
   if (!s || !buf || cap == 0 || B <= 0) return fail(QILQR_ERR_INVALID_ARG, "bad argument");
-  const long load_B = B;
+  // (the route of a device-resident batch solve with the handle's shared desired trajectory: nothing of the handle is touched)
+  const Route r = plan_route(route_inputs(s), B, CallFacts{s->dev.sync_every});
   std::string t;
-  const bool persistent = use_persistent(s, B);
-  const BackwardKind kind = persistent ? BW_FOUR : backward_kind(s, load_B);
-  if (kind == BW_ONE && !s->symmetric)
+  const bool persistent = r.persistent;
+  const BackwardKind kind = persistent ? BW_FOUR : r.backward;
+  if (kind == BW_ONE && !r.symmetric)
     t += "arithmetic: the reference's own forms (ilqr.hh:126-133: Eigen's diagonally pivoted LDL^T, V_x = Q_x - K^T Q_uu k, V_xx = Q_xx - K^T Q_uu K, "
          "not symmetrised)";
   else
@@ -2794,37 +2558,33 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
   t += s->f32 ? "; mixed precision (fp32 storage and lane-local arithmetic, fp64 recursion and cost sums)" : "; fp64";
   t += "; backward: ";
   t += persistent ? "k_solve4 (one launch per solve)" : kind == BW_FUSED ? "k_backward4, fused matrix + gradient wavefronts" : kind == BW_FOUR ? "k_backward4, six wavefronts"
-       : kind == BW_TWO ? "k_backward2" : s->modeled ? std::string("k_backward_models<") + (s->symmetric ? "true>" : "false>") +
-                                                        (s->limited ? " box form" : "") + ", one wavefront per trajectory"
-       : s->limited ? "k_backward<true> box form, one wavefront per trajectory"
-       : (s->symmetric ? "k_backward<true>, one wavefront per trajectory" : "k_backward<false>, one wavefront per trajectory (general kernel)");
-  if (kind == BW_FOUR || (kind == BW_FUSED && s->dev.force_general == 0 && load_B >= GFAC_MIN_LIVE))
+       : kind == BW_TWO ? "k_backward2" : r.backward_ext.models ? std::string("k_backward_models<") + (r.symmetric ? "true>" : "false>") +
+                                                        (r.backward_ext.limits ? " box form" : "") + ", one wavefront per trajectory"
+       : r.backward_ext.limits ? "k_backward<true> box form, one wavefront per trajectory"
+       : (r.symmetric ? "k_backward<true>, one wavefront per trajectory" : "k_backward<false>, one wavefront per trajectory (general kernel)");
+  if (kind == BW_FOUR || backward_now(r, B) != kind)
     t += kind == BW_FOUR ? " (Q_uu factored by the gradient wavefront in launches with " + std::to_string(GFAC_MIN_LIVE) + " or more running trajectories, by the matrix wavefronts otherwise: the same bits)"
                          : " (six wavefronts, Q_uu factored by the gradient wavefront, while " + std::to_string(GFAC_MIN_LIVE) + " or more trajectories run: the same bits)";
   if (!persistent) {
-    const int choice = s->dev.single_wave_rollout;
     t += "; rollout: ";
-    t += (s->integrator == 1 || s->limited || s->modeled || choice == 1) ? "k_rollout" : (choice == 3 || (choice == 0 && load_B <= R16_MAX_B)) ? "k_rollout16"
-         : choice == 0 ? "k_rollout3 for a trajectory's first " + std::to_string(ROLLOUT16_FROM) + " rollouts, k_rollout16 from there on" : "k_rollout3";
-    // (nothing of the handle is touched: the launch helpers take the batch and the record placement the call WOULD have)
-    const bool tiled = records_tiled(s, B, persistent);
-    const bool fused = fuse_backward_rollout(s, B, B, tiled) && s->dev.sync_every > 1;
-    const int parts = s->dev.sync_every > 1 ? auto_parts(s, B) : 1;
-    const bool compact = s->dev.compaction >= 0 && s->dev.sync_every > 1 && !s->modeled &&
-                         (s->dev.compaction == 1 || (!(fused && parts == 1) && kind != BW_ONE && tiled));
-    // the round's launch form by the predicate run_solve uses: the combined launch only where the compaction does not work between its halves
+    t += r.rollout == RO_LANE ? "k_rollout" : r.rollout == RO_16 ? "k_rollout16"
+         : r.rollout == RO_THREE_THEN_16 ? "k_rollout3 for a trajectory's first " + std::to_string(ROLLOUT16_FROM) + " rollouts, k_rollout16 from there on" : "k_rollout3";
+    const bool fused = r.combined && s->dev.sync_every > 1;
+    const int parts = r.parts;
+    const bool compact = r.compact;
+    // the round's launch form by the predicates the rounds use: the combined launch on one stream where the compaction does not work between its halves
     if (fused && parts == 1 && !compact)
-      t += round_kernel_ok(s) ? "; round: one launch (k_round), " + std::to_string(rounds_per_launch(s)) + " rounds per launch, while no other batch solve of the process is in flight on the device"
-                               : std::string("; round: k_backward_rollout + k_linearize");
-    else if (compact && fuse_kinds(s, B, B, tiled))
+      t += r.round_kernel ? "; round: one launch (k_round), " + std::to_string(r.rounds_per_launch) + " rounds per launch, while no other batch solve of the process is in flight on the device"
+                          : std::string("; round: k_backward_rollout + k_linearize");
+    else if (compact && r.fuse_kinds)
       t += "; round: three launches while the compaction runs, then " +
-           std::string(s->n_obstacles > 0 ? "k_backward_rollout + k_linearize (obstacles)" : "k_round (the mixed mode: k_backward_rollout + k_linearize)") +
+           std::string(r.linearize_ext.obstacles ? "k_backward_rollout + k_linearize (obstacles)" : "k_round (the mixed mode: k_backward_rollout + k_linearize)") +
            " once the running trajectories fit " + std::to_string(std::min(parts, 3)) + " block(s) of four per CU";
-    else if (long from = 0; compact && s->dev.compaction != 1 && late_tail_kinds(s, B, B, tiled, &from))
+    else if (compact && r.compaction != 1 && r.late_tail)
       t += "; round: three launches, then " +
-           std::string(s->n_obstacles > 0 ? "k_backward_rollout + k_linearize (the same bits; obstacles)" : "k_round (the same bits; the mixed mode: k_backward_rollout + k_linearize)") +
+           std::string(r.linearize_ext.obstacles ? "k_backward_rollout + k_linearize (the same bits; obstacles)" : "k_round (the same bits; the mixed mode: k_backward_rollout + k_linearize)") +
            " once the running trajectories fit " + std::to_string(std::min(parts, 3)) + " block(s) of four per CU"
-           + (from > 0 ? " and the rollouts are k_rollout16's (round " + std::to_string(from) + " on)" : std::string());
+           + (r.late_from > 0 ? " and the rollouts are k_rollout16's (round " + std::to_string(r.late_from) + " on)" : std::string());
     else
       t += "; round: three launches";
     t += "; sub-batch streams: " + std::to_string(parts);

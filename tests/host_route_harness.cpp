@@ -1,0 +1,80 @@
+// Host build of quadrotorilqr_amd/csrc/route.h for tests/test_route_cpu.py: one row of tests/golden/routes.json's inputs in, the
+// route's choices out, in the table's encoding.  Test scaffolding only.
+#include "../quadrotorilqr_amd/csrc/route.h"
+
+using namespace qilqr;
+
+namespace {
+long backward_code(const Route &r, long live) {
+  switch (backward_now(r, live)) {
+    case BW_ONE: return 0;
+    case BW_FUSED: return 1;
+    case BW_TWO: return 5;
+    default: return gradient_factors(r, live) ? 2 : r.many ? 3 : 4;
+  }
+}
+long ext_bits(const ExtArgs &x) { return (x.limits ? 1 : 0) | (x.models ? 2 : 0) | (x.obstacles ? 4 : 0); }
+}  // namespace
+
+extern "C" int hr_route(const long *in, long *out) {
+  RouteInputs ri;
+  const long fg = in[9];
+  ri.symmetric = in[0] && fg != 1;                    // (qilqr_create: force_general = 1 takes the general forms)
+  const bool q_sym = in[1] && fg != 1, ur_zero = in[2];
+  ri.layout_kind = !q_sym ? 0 : (ur_zero ? 2 : 1);   // (se3_math.h, layout_kind)
+  ri.q_diag = in[3];
+  ri.f32 = in[4];
+  ri.integrator = (int)in[5];
+  ri.limited = in[6];
+  ri.modeled = in[7];
+  ri.obstacles = in[8];
+  ri.dev.force_general = (int)fg;
+  ri.dev.single_wave_rollout = (int)in[10];
+  ri.dev.round_launch = (int)in[11];
+  ri.dev.compaction = (int)in[12];
+  ri.dev.streams = (int)in[13];
+  ri.dev.persistent = (int)in[14];
+  ri.dev.rounds_per_launch = (int)in[15];
+  ri.dev.sync_every = (int)in[16];
+  const long B = in[17];
+  ri.hw_queues = (int)in[18];
+  ri.num_cus = 256;
+  CallFacts call;
+  call.sync_every = (int)in[16];
+  call.desired_batch = in[19];
+  call.cost_hist = in[20];
+  call.early_out = in[21];
+  call.iterates = in[22];
+  const Route r = plan_route(ri, B, call);
+  const TailFuse tf = tail_fuse(r, r.compact, r.parts);
+  long *o = out;
+  *o++ = r.persistent;
+  *o++ = r.tiled;
+  *o++ = r.backward;
+  *o++ = r.backward == BW_ONE ? ext_bits(r.backward_ext) : 0;
+  *o++ = r.rollout == RO_LANE ? 0 : r.rollout == RO_16 ? 1 : r.rollout == RO_THREE ? 2 : 3;
+  *o++ = r.rollout == RO_LANE ? ext_bits(r.rollout_ext) : 0;
+  *o++ = r.lin_kind;
+  *o++ = ext_bits(r.linearize_ext);
+  *o++ = r.tiled;
+  *o++ = r.fuse_kinds;
+  *o++ = r.combined;
+  *o++ = r.round_kernel;
+  *o++ = r.rounds_per_launch;
+  *o++ = r.late_tail;
+  *o++ = r.late_from;
+  *o++ = r.parts;
+  *o++ = r.compact;
+  *o++ = tf.kinds;
+  *o++ = tf.slots;
+  *o++ = tf.stop;
+  *o++ = tf.from;
+  for (long live : {B, 1L, 3071L, 3072L}) *o++ = backward_code(r, live);
+  *o++ = (r.round_kernel && (r.fuse_kinds || r.late_tail)) ? r.lin_kind : -1;
+  for (long seen : {B, std::max(1L, B / 8)}) {
+    *o++ = round_form(r, false, true, (unsigned)seen, B).six;
+    *o++ = round_form(r, true, true, (unsigned)seen, B).six;
+    *o++ = round_form(r, true, false, (unsigned)seen, B).six;
+  }
+  return (int)(o - out);
+}

@@ -137,6 +137,20 @@ def test_late_rounds_of_a_large_batch_take_the_combined_launch(B, N, kw):
         h.close()
 
 
+def test_describe_reports_what_two_streams_at_1024_do():
+    """A batch of 1024 on two sub-batch streams: its kernels are the two the combined launch stands for, so the compaction stays off, and the
+    sub-batch streams launch them apart.  qilqr_describe says so (it renders the route the solve takes), and the solve moves nothing."""
+    cfg = pb.config2(B=1024, N=40, seed=13)
+    s = capi.from_config(cfg, streams=2, profile=1)
+    d = s.describe(1024)
+    assert "compaction: off" in d and "k_round" not in d and "sub-batch streams: 2" in d, d
+    out = solve_device(s, cfg["init"])
+    assert (out["status"] >= 0).all() and np.isfinite(out["traj"]).all()
+    assert s.compaction_moves() == 0
+    assert s.profile_get()["rollout_launches"] > 0  # three launches per round: the rollouts have launches of their own
+    s.close()
+
+
 def test_bad_value_is_refused():
     cfg = pb.config2(B=4, N=10)
     with pytest.raises(TypeError, match="compaction"):

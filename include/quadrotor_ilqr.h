@@ -337,6 +337,24 @@ int qilqr_set_batch_models(qilqr_solver *s, const qilqr_model *models, int32_t B
 #define QILQR_MAX_OBSTACLES 64
 int qilqr_set_obstacles(qilqr_solver *s, const double *spheres, int32_t count);
 
+/* Per-problem, moving spheres -- an EXTENSION beside qilqr_set_obstacles: problem b of the batch gets its own counts[b] <= K spheres,
+ * for a fleet in its own surroundings, receding-horizon use with predicted obstacles, or sampled obstacle fields.  spheres is
+ * B x K x QILQR_OBSTACLE_WORDS doubles (row-major) {cx, cy, cz, vx, vy, vz, radius, weight}; counts (int32[B]) may be NULL for all K.
+ * At knot i (0-based, the last included) the centre is c + t_i v, t_i = i dt (dt the handle's), per axis fma(t_i, v, c): a sphere
+ * with v = 0 is centred at c exactly.  From there the term, its gradient and Gauss-Newton block, the d == 0 rule and "an inactive
+ * sphere touches nothing" are those of qilqr_set_obstacles, by the same arithmetic (a static sphere here gives the bits of the same
+ * shared sphere).  A caller who solves from time t0 shifts c by t0 v.  Order within a knot cost: the tracking cost, the handle's
+ * shared spheres, then the problem's own, each in index order; both tables may be set at once.  Rows j >= counts[b] are never read.
+ * Used by every entry point that evaluates or differentiates the cost (qilqr_solve_batch[_device], qilqr_cost_trajectory,
+ * qilqr_backwards_pass, qilqr_line_search, the cost history, and qilqr_solve as B = 1), each of which is then refused for another B;
+ * qilqr_forward_sim evaluates no cost and takes any B.  Composes as the shared spheres do (the compaction included: the table is read
+ * by the problem's row).  Validates, re-lays the table out for the device (tiles of 64 problems) and uploads it once, and waits for the
+ * handle's stream.  QILQR_ERR_INVALID_ARG, with the reason and the first bad (problem, sphere) in qilqr_last_error, for K outside
+ * 1 ... QILQR_MAX_OBSTACLES, a count outside 0 ... K, a non-finite word in a used row, radius <= 0, weight < 0, a mixed-precision
+ * handle, and, while the table is set, a solve with persistent = 1.  spheres = counts = NULL with B = K = 0 clears the table. */
+#define QILQR_OBSTACLE_WORDS 8
+int qilqr_set_batch_obstacles(qilqr_solver *s, const double *spheres, const int32_t *counts, int32_t B, int32_t K);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -426,6 +444,11 @@ int qilqr_sharded_set_batch_models(qilqr_sharded *h, const qilqr_model *models, 
 /* qilqr_set_obstacles on every shard's solver (the same spheres for the whole batch); checked once first, and a failure leaves
  * every shard without obstacles.  NULL, 0 clears them. */
 int qilqr_sharded_set_obstacles(qilqr_sharded *h, const double *spheres, int32_t count);
+
+/* qilqr_set_batch_obstacles for a sharded handle: shard r's solver gets rows [begin, begin + count) (qilqr_shard_range of B), and the
+ * sharded solves refuse another B.  The whole batch is checked first (the index in an error is the batch's); a failure leaves every
+ * shard cleared.  NULL, NULL, 0, 0 clears. */
+int qilqr_sharded_set_batch_obstacles(qilqr_sharded *h, const double *spheres, const int32_t *counts, int32_t B, int32_t K);
 const char *qilqr_sharded_transport(qilqr_sharded *h);
 int qilqr_solve_batch_sharded_device(qilqr_sharded *h, const double *init, const double *desired_batch, int32_t B, int32_t n,
                                      int32_t root, double *d_out_traj, double *d_out_cost, int32_t *d_out_status,
@@ -456,7 +479,8 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
 /* ABI version of this header: 7 (qilqr_device_config grew by round_launch, rounds_per_launch, fuse_in_flight, dense_weights -- the
  * switches that were environment variables -- and the *_sized entry points carry the caller's structure size; version 6 added
  * `compaction`).  qilqr_set_control_limits, QILQR_STATUS_QP_FAILED, qilqr_set_batch_models, qilqr_sharded_set_batch_models,
- * qilqr_set_obstacles, qilqr_sharded_set_obstacles and QILQR_MAX_OBSTACLES were added within version 7: no structure changed. */
+ * qilqr_set_obstacles, qilqr_sharded_set_obstacles, QILQR_MAX_OBSTACLES, qilqr_set_batch_obstacles, qilqr_sharded_set_batch_obstacles
+ * and QILQR_OBSTACLE_WORDS were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

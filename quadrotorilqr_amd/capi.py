@@ -32,7 +32,8 @@ STATUS_CONVERGED = 1
 STATUS_MAX_ITERS = 2
 STATUS_LINE_SEARCH_FAILED = 3
 STATUS_QP_FAILED = 4  # extension: a knot's box QP broke down (set_control_limits)
-MAX_OBSTACLES = 64  # QILQR_MAX_OBSTACLES: spheres per handle (set_obstacles)
+MAX_OBSTACLES = 64  # QILQR_MAX_OBSTACLES: spheres per handle (set_obstacles), and per problem (set_batch_obstacles)
+OBSTACLE_WORDS = 8  # QILQR_OBSTACLE_WORDS: {cx, cy, cz, vx, vy, vz, radius, weight} of a per-problem sphere (set_batch_obstacles)
 
 # every symbol include/quadrotor_ilqr.h declares
 EXPORTS = (
@@ -40,7 +41,7 @@ EXPORTS = (
     "qilqr_solve_batch_device", "qilqr_cost_trajectory", "qilqr_backwards_pass", "qilqr_forward_sim",
     "qilqr_line_search", "qilqr_cost_history", "qilqr_profile_reset", "qilqr_profile_get", "qilqr_profile_mode", "qilqr_set_regularisation",
     "qilqr_set_integrator", "qilqr_set_control_limits", "qilqr_set_batch_models", "qilqr_sharded_set_batch_models",
-    "qilqr_set_obstacles", "qilqr_sharded_set_obstacles",
+    "qilqr_set_obstacles", "qilqr_sharded_set_obstacles", "qilqr_set_batch_obstacles", "qilqr_sharded_set_batch_obstacles",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -106,6 +107,8 @@ def load():
         lib.qilqr_sharded_set_batch_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         lib.qilqr_set_obstacles.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
         lib.qilqr_sharded_set_obstacles.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
+        for f in (lib.qilqr_set_batch_obstacles, lib.qilqr_sharded_set_batch_obstacles):
+            f.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32, C.c_int32]
         _lib = lib
     return _lib
 
@@ -214,6 +217,27 @@ def obstacle_array(spheres):
         raise TypeError(f"obstacles: a (K, 5) array of spheres {{cx, cy, cz, radius, weight}}, K >= 1; got shape {arr.shape} "
                         "(clear_obstacles() switches them off)")
     return arr
+
+
+def batch_obstacle_arrays(spheres, counts=None):
+    """(B, K, 8) float64 spheres {cx, cy, cz, vx, vy, vz, radius, weight} and int32[B] counts (or None) for qilqr_set_batch_obstacles;
+    (B, K, 5) rows {cx, cy, cz, radius, weight} are static spheres (v = 0).  The library checks the values."""
+    arr = np.asarray(spheres, dtype=np.float64)
+    if arr.ndim != 3 or arr.shape[2] not in (5, OBSTACLE_WORDS) or arr.shape[0] == 0 or arr.shape[1] == 0:
+        raise TypeError(f"batch obstacles: a (B, K, 8) array {{cx, cy, cz, vx, vy, vz, radius, weight}} or a (B, K, 5) array of static "
+                        f"spheres {{cx, cy, cz, radius, weight}}, B, K >= 1; got shape {arr.shape} (clear_batch_obstacles() switches them off)")
+    if arr.shape[2] == 5:
+        full = np.zeros(arr.shape[:2] + (OBSTACLE_WORDS,))
+        full[..., :3] = arr[..., :3]
+        full[..., 6:] = arr[..., 3:]
+        arr = full
+    arr = _d(arr)
+    if counts is not None:
+        counts = np.asarray(counts)
+        if counts.shape != (arr.shape[0],) or not np.issubdtype(counts.dtype, np.integer):
+            raise TypeError(f"batch obstacles: counts must be {arr.shape[0]} integers, one per problem; got {counts.dtype} {counts.shape}")
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+    return arr, counts
 
 
 def _raise_models(rc):
@@ -484,6 +508,21 @@ class QuadrotorILQRBatch:
         if rc:
             _raise(rc)
 
+    def set_batch_obstacles(self, spheres, counts=None):
+        """Per-problem, moving spheres (an extension): `spheres` is (B, K, 8) {cx, cy, cz, vx, vy, vz, radius, weight} or (B, K, 5) static
+        {cx, cy, cz, radius, weight}; problem b uses its first counts[b] rows (all K without counts).  At knot i the centre is c + i dt v.
+        Every call that evaluates the cost is then over exactly B problems -- see qilqr_set_batch_obstacles in include/quadrotor_ilqr.h.
+        clear_batch_obstacles() switches them off again."""
+        arr, cnt = batch_obstacle_arrays(spheres, counts)
+        rc = load().qilqr_set_batch_obstacles(self._h, _p(arr), _ip(cnt), C.c_int32(arr.shape[0]), C.c_int32(arr.shape[1]))
+        if rc:
+            _raise(rc)
+
+    def clear_batch_obstacles(self):
+        rc = load().qilqr_set_batch_obstacles(self._h, None, None, C.c_int32(0), C.c_int32(0))
+        if rc:
+            _raise(rc)
+
     def profile_get(self):
         p = Profile()
         rc = load().qilqr_profile_get(self._h, C.byref(p))
@@ -577,6 +616,18 @@ class QuadrotorILQRSharded:
 
     def clear_obstacles(self):
         rc = load().qilqr_sharded_set_obstacles(self._h, None, C.c_int32(0))
+        if rc:
+            _raise(rc)
+
+    def set_batch_obstacles(self, spheres, counts=None):
+        """QuadrotorILQRBatch.set_batch_obstacles for the sharded batch: each shard's solver gets its rows (qilqr_sharded_set_batch_obstacles)"""
+        arr, cnt = batch_obstacle_arrays(spheres, counts)
+        rc = load().qilqr_sharded_set_batch_obstacles(self._h, _p(arr), _ip(cnt), C.c_int32(arr.shape[0]), C.c_int32(arr.shape[1]))
+        if rc:
+            _raise(rc)
+
+    def clear_batch_obstacles(self):
+        rc = load().qilqr_sharded_set_batch_obstacles(self._h, None, None, C.c_int32(0), C.c_int32(0))
         if rc:
             _raise(rc)
 

@@ -76,6 +76,11 @@ struct qilqr_solver {
   int n_obstacles = 0;          // spherical obstacles in the cost (qilqr_set_obstacles): k_linearize adds them, k_round never runs
   double *d_obstacles = nullptr;   // ... the table in device memory, [OB_MAX][OB_WORDS] (obstacles.h), allocated at the first setter call
   std::vector<double> obstacles;   // ... and its host copy (qilqr_describe)
+  long pobs_B = 0;                 // per-problem spheres (qilqr_set_batch_obstacles) for this many problems (0: none): every call of exactly pobs_B
+  int pobs_K = 0, pobs_max = 0;    // ... K spheres per problem, the largest count
+  bool pobs_moving = false;        // ... whether any used sphere has v != 0
+  double *d_pobs = nullptr;        // ... the table in device memory, bob_count(pobs_B, pobs_K) doubles (obstacles.h, bob_index)
+  int *d_pobs_counts = nullptr;    // ... and the counts, int32[pobs_B]
   ModelConsts<float> constsf;   // the model constants for the fp32 lane-local kernels
   // workspace
   long cap_B = 0, cap_n = 0;
@@ -357,11 +362,12 @@ int hw_queues() {
 // what of the handle the route reads (models = false: a call that ignores the per-problem models, qilqr_cost_trajectory)
 RouteInputs route_inputs(const qilqr_solver *s, bool models = true) {
   return RouteInputs{s->symmetric, s->q_diag, layout_kind(s->layout), s->f32, s->integrator, s->limited, s->modeled && models,
-                     s->n_obstacles > 0, s->dev, s->num_cus, hw_queues()};
+                     s->n_obstacles > 0 || s->pobs_B > 0, s->dev, s->num_cus, hw_queues(), s->pobs_B > 0};
 }
 // the entry point a call comes through: a batch solve, qilqr_solve, a stand-alone pass, or qilqr_cost_trajectory (which ignores the models:
-// the cost does not depend on the model, and a call of any B takes the handle's own route)
-enum Entry { E_BATCH, E_SOLVE, E_PASS, E_COST };
+// the cost does not depend on the model, and a call of any B takes the handle's own route); E_SIM: qilqr_forward_sim, a pass that
+// evaluates no cost (it ignores the per-problem spheres)
+enum Entry { E_BATCH, E_SOLVE, E_PASS, E_COST, E_SIM };
 // The calls a handle refuses for what its extensions cannot do (the setters check the values they are given)
 int refuse(const qilqr_solver *s, long B, Entry call) {
   if (call == E_BATCH && s->dev.persistent == 1) {
@@ -370,7 +376,14 @@ int refuse(const qilqr_solver *s, long B, Entry call) {
       return fail(QILQR_ERR_INVALID_ARG, "batch models: persistent = 1 (k_solve4) has one model for the batch; take the rounds (persistent = 0)");
     if (s->n_obstacles > 0)
       return fail(QILQR_ERR_INVALID_ARG, "obstacles: persistent = 1 (k_solve4) linearises without them; take the rounds (persistent = 0)");
+    if (s->pobs_B > 0)
+      return fail(QILQR_ERR_INVALID_ARG, "batch obstacles: persistent = 1 (k_solve4) linearises without them; take the rounds (persistent = 0)");
   }
+  // per-problem spheres (qilqr_set_batch_obstacles): problem b reads row b, so every call that evaluates the cost is over the rows they were
+  // set for (qilqr_solve: B = 1)
+  if (call != E_SIM && s->pobs_B > 0 && B != s->pobs_B)
+    return fail(QILQR_ERR_INVALID_ARG, "batch obstacles were set for B = " + std::to_string(s->pobs_B) + " problems; this call has B = " +
+                                           std::to_string(B) + " (set them again, or clear them, for another batch)");
   if (call == E_SOLVE && s->modeled)
     return fail(QILQR_ERR_INVALID_ARG, "batch models are set: qilqr_solve solves one problem with the handle's model; use qilqr_solve_batch, or "
                                        "clear the models");
@@ -455,17 +468,40 @@ int lin(qilqr_solver *s, long B, long n, int which, int need_flag, int round, Ex
   return QILQR_OK;
 }
 constexpr int lin_key(int lk, int integ, bool tiled, bool f32, int ext) { return lk + 4 * integ + 8 * tiled + 16 * f32 + 32 * ext; }
-enum { LIN_PLAIN, LIN_MODELS, LIN_OBSTACLES, LIN_BOTH };
+enum { LIN_PLAIN, LIN_MODELS, LIN_OBSTACLES, LIN_BOTH, LIN_PROBLEM = 4 };
 int launch_linearize(qilqr_solver *s, long B, long n, int which, int need_flag, int round = -1) {
   const Route &r = s->route;
   const BatchModels bm{s->d_models};
   const Obstacles ob{s->d_obstacles, s->n_obstacles};
   const ModelsObstacles mo{bm, ob};
-  const int ext = (r.linearize_ext.models ? LIN_MODELS : LIN_PLAIN) | (r.linearize_ext.obstacles ? LIN_OBSTACLES : LIN_PLAIN);
+  // the per-problem spheres by the problem's row: a compacting batch solve moves trajectories between slots, and from its first candidate
+  // linearisation on (which = 1: behind k_init, which writes the map) the row of a slot is st.orig's
+  const ProblemObstacles po{ob, s->d_pobs, s->d_pobs_counts, s->pobs_K, (s->compact && which == 1) ? 1 : 0};
+  const ModelsProblemObstacles mpo{bm, po};
+  const int ext = (r.linearize_ext.models ? LIN_MODELS : LIN_PLAIN) | (r.linearize_ext.obstacles ? LIN_OBSTACLES : LIN_PLAIN) |
+                  (r.linearize_ext.problem_obstacles ? LIN_PROBLEM : LIN_PLAIN);
   // Every instantiation the routes take, and no other: the extensions are fp64 and plain-placed but for the obstacles' tiled records (the
   // symmetric kinds), the Runge-Kutta records (INTEG = 1) are plain and have no diagonal kind.  (The placement of the records, s->st.layout.tiled,
   // was chosen with the call's backward kernel: Route::tiled.)
   switch (lin_key(r.lin_kind, r.integrator, s->st.layout.tiled != 0, r.f32, ext)) {
+    // the per-problem spheres (with or without shared ones): the obstacle route's instantiations, in the form that carries both tables
+    case lin_key(0, 0, false, false, LIN_BOTH | LIN_PROBLEM): return lin<double, 0, 0, false>(s, B, n, which, need_flag, round, mpo);
+    case lin_key(1, 0, false, false, LIN_BOTH | LIN_PROBLEM): return lin<double, 1, 0, false>(s, B, n, which, need_flag, round, mpo);
+    case lin_key(2, 0, false, false, LIN_BOTH | LIN_PROBLEM): return lin<double, 2, 0, false>(s, B, n, which, need_flag, round, mpo);
+    case lin_key(3, 0, false, false, LIN_BOTH | LIN_PROBLEM): return lin<double, 3, 0, false>(s, B, n, which, need_flag, round, mpo);
+    case lin_key(0, 1, false, false, LIN_BOTH | LIN_PROBLEM): return lin<double, 0, 1, false>(s, B, n, which, need_flag, round, mpo);
+    case lin_key(1, 1, false, false, LIN_BOTH | LIN_PROBLEM): return lin<double, 1, 1, false>(s, B, n, which, need_flag, round, mpo);
+    case lin_key(2, 1, false, false, LIN_BOTH | LIN_PROBLEM): return lin<double, 2, 1, false>(s, B, n, which, need_flag, round, mpo);
+    case lin_key(0, 0, false, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 0, 0, false>(s, B, n, which, need_flag, round, po);
+    case lin_key(1, 0, false, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 1, 0, false>(s, B, n, which, need_flag, round, po);
+    case lin_key(2, 0, false, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 2, 0, false>(s, B, n, which, need_flag, round, po);
+    case lin_key(3, 0, false, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 3, 0, false>(s, B, n, which, need_flag, round, po);
+    case lin_key(0, 1, false, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 0, 1, false>(s, B, n, which, need_flag, round, po);
+    case lin_key(1, 1, false, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 1, 1, false>(s, B, n, which, need_flag, round, po);
+    case lin_key(2, 1, false, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 2, 1, false>(s, B, n, which, need_flag, round, po);
+    case lin_key(1, 0, true, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 1, 0, true>(s, B, n, which, need_flag, round, po);
+    case lin_key(2, 0, true, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 2, 0, true>(s, B, n, which, need_flag, round, po);
+    case lin_key(3, 0, true, false, LIN_OBSTACLES | LIN_PROBLEM): return lin<double, 3, 0, true>(s, B, n, which, need_flag, round, po);
     case lin_key(0, 0, false, false, LIN_BOTH): return lin<double, 0, 0, false>(s, B, n, which, need_flag, round, mo);
     case lin_key(1, 0, false, false, LIN_BOTH): return lin<double, 1, 0, false>(s, B, n, which, need_flag, round, mo);
     case lin_key(2, 0, false, false, LIN_BOTH): return lin<double, 2, 0, false>(s, B, n, which, need_flag, round, mo);
@@ -1442,6 +1478,8 @@ void qilqr_destroy(qilqr_solver *s) {
   if (s->d_ctab) (void)hipFree(s->d_ctab);
   if (s->d_models) (void)hipFree(s->d_models);
   if (s->d_obstacles) (void)hipFree(s->d_obstacles);
+  if (s->d_pobs) (void)hipFree(s->d_pobs);
+  if (s->d_pobs_counts) (void)hipFree(s->d_pobs_counts);
   if (s->d_consts) (void)hipFree(s->d_consts);
   if (s->h_counters) (void)hipHostFree(s->h_counters);
   if (s->h_active) (void)hipHostFree(s->h_active);
@@ -1633,6 +1671,62 @@ int qilqr_set_obstacles(qilqr_solver *s, const double *spheres, int32_t count) {
     if (!s->d_obstacles) HIP_TRY(hipMalloc((void **)&s->d_obstacles, sizeof(double) * OB_MAX * OB_WORDS));
     HIP_TRY(hipMemcpy(s->d_obstacles, spheres, sizeof(double) * (size_t)count * OB_WORDS, hipMemcpyHostToDevice));
     s->n_obstacles = count;
+  }
+  return QILQR_OK;
+}
+
+namespace {
+// qilqr_set_batch_obstacles' checks of a table (obstacles.h, bob_check), shared with the sharded setter; the index is the batch's
+int check_batch_obstacles(const double *spheres, const int32_t *counts, int32_t B, int32_t K) {
+  BobCheck e;
+  if (!bob_check(spheres, counts, B, K, QILQR_MAX_OBSTACLES, &e)) return QILQR_OK;
+  std::string at;
+  if (e.b >= 0) at = " (problem " + std::to_string(e.b) + (e.j >= 0 ? ", sphere " + std::to_string(e.j) : std::string()) + ")";
+  return fail(QILQR_ERR_INVALID_ARG, std::string("batch obstacles: ") + e.why + at);
+}
+}  // namespace
+
+static_assert(OB_BWORDS == QILQR_OBSTACLE_WORDS, "obstacles.h and the C header agree on a per-problem sphere's words");
+int qilqr_set_batch_obstacles(qilqr_solver *s, const double *spheres, const int32_t *counts, int32_t B, int32_t K) {
+  if (!s) return fail(QILQR_ERR_INVALID_ARG, "null solver");
+  int rc = check_batch_obstacles(spheres, counts, B, K);
+  if (rc) return rc;
+  if (B > 0 && s->f32)
+    return fail(QILQR_ERR_INVALID_ARG, "batch obstacles need precision 0 (fp64): the mixed-precision kernels have no obstacle form");
+  // the device layout and the counts on the host (the caller's rows re-laid once, here)
+  std::vector<double> tab;
+  std::vector<int32_t> cnt;
+  int kmax = 0;
+  bool moving = false;
+  if (B > 0) {
+    tab.resize((size_t)bob_count(B, K));
+    bob_relayout(spheres, B, K, tab.data());
+    cnt.resize((size_t)B);
+    for (int32_t b = 0; b < B; ++b) {
+      cnt[b] = counts ? counts[b] : K;
+      kmax = std::max(kmax, (int)cnt[b]);
+      for (int32_t j = 0; j < cnt[b]; ++j)
+        for (int w = OB_BV; w < OB_BV + 3; ++w) moving = moving || spheres[((size_t)b * K + j) * OB_BWORDS + w] != 0.0;
+    }
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));  // (no launch of this handle still reads the table)
+  s->pobs_B = 0;
+  s->pobs_K = s->pobs_max = 0;
+  s->pobs_moving = false;
+  if (s->d_pobs) (void)hipFree(s->d_pobs);
+  if (s->d_pobs_counts) (void)hipFree(s->d_pobs_counts);
+  s->d_pobs = nullptr;
+  s->d_pobs_counts = nullptr;
+  if (B > 0) {
+    HIP_TRY(hipMalloc((void **)&s->d_pobs, sizeof(double) * tab.size()));
+    HIP_TRY(hipMalloc((void **)&s->d_pobs_counts, sizeof(int32_t) * cnt.size()));
+    HIP_TRY(hipMemcpy(s->d_pobs, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_pobs_counts, cnt.data(), sizeof(int32_t) * cnt.size(), hipMemcpyHostToDevice));
+    s->pobs_B = B;
+    s->pobs_K = K;
+    s->pobs_max = kmax;
+    s->pobs_moving = moving;
   }
   return QILQR_OK;
 }
@@ -1889,7 +1983,7 @@ int qilqr_backwards_pass(qilqr_solver *s, const double *traj, int32_t B, int32_t
 int qilqr_forward_sim(qilqr_solver *s, const double *traj, const double *gains, const double *alpha, int32_t B,
                       int32_t n, double *out_traj) {
   if (!s || !traj || !gains || !alpha || !out_traj) return fail(QILQR_ERR_INVALID_ARG, "null argument");
-  int rc = begin_batch(s, B, n, nullptr, E_PASS);
+  int rc = begin_batch(s, B, n, nullptr, E_SIM);
   if (rc) return rc;
   if ((rc = upload_tiled(s, traj, s->st.traj[0], B, n, 18))) return rc;
   if ((rc = upload_tiled(s, gains, s->st.gains, B, n, 52))) return rc;
@@ -2047,6 +2141,7 @@ struct qilqr_sharded {
   std::mutex gather_mutex;               // the shards' host threads enqueue their transfers one at a time (shared communicators / streams)
   std::string info;
   int32_t models_B = -1;                 // per-problem models set for this many problems (qilqr_sharded_set_batch_models), -1: none
+  int32_t pobs_B = -1;                   // per-problem spheres set for this many problems (qilqr_sharded_set_batch_obstacles), -1: none
 };
 
 extern "C++" {
@@ -2289,6 +2384,8 @@ int qilqr_solve_batch_sharded(qilqr_sharded *h, const double *init, const double
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
   if (h->models_B >= 0 && B != h->models_B)  // (a shard with no rows of the models' batch has none set: checked here, for the whole batch)
     return fail(QILQR_ERR_INVALID_ARG, "batch models were set for B = " + std::to_string(h->models_B) + " problems; this call has B = " + std::to_string(B));
+  if (h->pobs_B >= 0 && B != h->pobs_B)  // (likewise for the per-problem spheres)
+    return fail(QILQR_ERR_INVALID_ARG, "batch obstacles were set for B = " + std::to_string(h->pobs_B) + " problems; this call has B = " + std::to_string(B));
   DeviceGuard guard;
   try {
     const ShardCall c{init, desired_batch, B, n, out_traj, out_cost, out_status, out_iters, out_n_bwd, out_n_fwd, true};
@@ -2341,6 +2438,35 @@ int qilqr_sharded_set_obstacles(qilqr_sharded *h, const double *spheres, int32_t
       return fail(rc, msg);
     }
   }
+  return QILQR_OK;
+}
+
+int qilqr_sharded_set_batch_obstacles(qilqr_sharded *h, const double *spheres, const int32_t *counts, int32_t B, int32_t K) {
+  if (!h || h->solvers.empty()) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  // (the whole batch is checked before any shard is set, so the index in an error is the batch's; any failure leaves every shard cleared)
+  int rc = check_batch_obstacles(spheres, counts, B, K);
+  if (!rc && B > 0 && h->solvers[0]->f32)
+    rc = fail(QILQR_ERR_INVALID_ARG, "batch obstacles need precision 0 (fp64): the mixed-precision kernels have no obstacle form");
+  const int32_t k = (int32_t)h->solvers.size();
+  DeviceGuard guard;
+  h->pobs_B = -1;
+  if (rc) {
+    const std::string msg = g_last_error;
+    for (qilqr_solver *q : h->solvers) (void)qilqr_set_batch_obstacles(q, nullptr, nullptr, 0, 0);
+    return fail(rc, msg);
+  }
+  for (int32_t r = 0; r < k; ++r) {
+    int32_t b0 = 0, cnt = 0;
+    (void)qilqr_shard_range(B, k, r, &b0, &cnt);
+    rc = cnt ? qilqr_set_batch_obstacles(h->solvers[r], spheres + (size_t)b0 * K * OB_BWORDS, counts ? counts + b0 : nullptr, cnt, K)
+             : qilqr_set_batch_obstacles(h->solvers[r], nullptr, nullptr, 0, 0);
+    if (rc) {  // (none half set: every shard cleared)
+      const std::string msg = g_last_error;
+      for (qilqr_solver *q : h->solvers) (void)qilqr_set_batch_obstacles(q, nullptr, nullptr, 0, 0);
+      return fail(rc, msg);
+    }
+  }
+  if (B > 0) h->pobs_B = B;
   return QILQR_OK;
 }
 
@@ -2463,6 +2589,8 @@ int qilqr_solve_batch_sharded_device(qilqr_sharded *h, const double *init, const
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
   if (h->models_B >= 0 && B != h->models_B)
     return fail(QILQR_ERR_INVALID_ARG, "batch models were set for B = " + std::to_string(h->models_B) + " problems; this call has B = " + std::to_string(B));
+  if (h->pobs_B >= 0 && B != h->pobs_B)
+    return fail(QILQR_ERR_INVALID_ARG, "batch obstacles were set for B = " + std::to_string(h->pobs_B) + " problems; this call has B = " + std::to_string(B));
   const int32_t k = (int32_t)h->solvers.size();
   if (root < 0 || root >= k) return fail(QILQR_ERR_INVALID_ARG, "root must be a shard index");
   DeviceGuard guard;
@@ -2555,6 +2683,11 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
     }
     t += ", penalised in the knot cost by k_linearize (the rounds never take the kernels that linearise inside themselves)";
   }
+  if (s->pobs_B > 0)
+    t += "; batch obstacles (extension): per-problem spheres for B = " + std::to_string(s->pobs_B) + " problems, K = " + std::to_string(s->pobs_K) +
+         ", at most " + std::to_string(s->pobs_max) + " used per problem, " + (s->pobs_moving ? "some moving" : "none moving") +
+         ", penalised in the knot cost by k_linearize (the rounds never take the kernels that linearise inside themselves)" +
+         (B != s->pobs_B ? " (a call of B = " + std::to_string(B) + " problems is refused)" : std::string());
   t += s->f32 ? "; mixed precision (fp32 storage and lane-local arithmetic, fp64 recursion and cost sums)" : "; fp64";
   t += "; backward: ";
   t += persistent ? "k_solve4 (one launch per solve)" : kind == BW_FUSED ? "k_backward4, fused matrix + gradient wavefronts" : kind == BW_FOUR ? "k_backward4, six wavefronts"
@@ -2645,6 +2778,8 @@ int qilqr_debug_set_backward_stall(qilqr_solver *s, int32_t rec) {
 // stream runs k_linearize launches back to back (beside = 1).  us[0]: microseconds per rollout launch; us[1]: per
 // linearisation launch.  Timing only: the linearisation reads the candidate while it is being written.
 int qilqr_debug_rollout_beside_linearize(qilqr_solver *s, int32_t B, int32_t n, int32_t reps, int32_t beside, float *us) {
+  if (beside && s->pobs_B > 0 && B != s->pobs_B)  // (k_linearize reads the per-problem spheres of rows 0 .. B - 1)
+    return fail(QILQR_ERR_INVALID_ARG, "batch obstacles were set for B = " + std::to_string(s->pobs_B) + " problems");
   HIP_TRY(hipSetDevice(s->device));
   int rc;
   if ((rc = ensure_parts(s, 1))) return rc;

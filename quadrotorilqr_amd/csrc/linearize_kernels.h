@@ -23,6 +23,10 @@ namespace qilqr {
 // cost half adds the spheres' penalties (obstacles.h) to the knot cost, C_x and the pose block of C_xx behind linearize_cost, in the
 // record positions of the layout kind.  The table sits in LDS, one copy per cost wavefront, filled beside Q and R: the obstacle index
 // is wave-uniform, so every lane reads the same word.
+// Mod = ProblemObstacles (fp64, either placement), or ModelsProblemObstacles (plain, with the per-problem models): the per-problem,
+// moving spheres (qilqr_set_batch_obstacles) behind the shared ones of the same argument.  That table is not wave-uniform: each lane
+// reads its problem's row from global memory (obstacles.h, bob_index: without compaction one 512-byte load per word for the wavefront),
+// and the wavefront runs to the largest count among its lanes, the lanes past their own doing nothing.
 // ---------------------------------------------------------------------------------------------
 #ifndef QILQR_LIN_BLOCK
 #define QILQR_LIN_BLOCK 128
@@ -39,9 +43,10 @@ template <typename S, int LK, int INTEG, bool TILED, typename... Mod>
 __global__ __launch_bounds__(QILQR_LIN_BLOCK) __attribute__((amdgpu_waves_per_eu(QILQR_LIN_WAVES, QILQR_LIN_WAVES))) void
 k_linearize(ModelConsts<S> c, const ModelConsts<S> *__restrict__ cp, BatchState st, int B, int n, int which,
             int need_flag, int round, Mod... mod) {
-  constexpr bool MOD = pack_has<BatchModels, Mod...> || pack_has<ModelsObstacles, Mod...>;
+  constexpr bool MOD = pack_has<BatchModels, Mod...> || pack_has<ModelsObstacles, Mod...> || pack_has<ModelsProblemObstacles, Mod...>;
   static_assert(!MOD || (std::is_same<S, double>::value && !TILED), "the per-problem models are an fp64 extension on plain records");
-  constexpr bool OBS = pack_has<Obstacles, Mod...> || pack_has<ModelsObstacles, Mod...>;
+  constexpr bool POBS = pack_has<ProblemObstacles, Mod...> || pack_has<ModelsProblemObstacles, Mod...>;  // per-problem spheres
+  constexpr bool OBS = pack_has<Obstacles, Mod...> || pack_has<ModelsObstacles, Mod...> || POBS;
   static_assert(!OBS || std::is_same<S, double>::value, "the obstacles are an fp64 extension");
   // The weights Q (144) and R (16) are more constants than a wave has scalar registers: the block keeps
   // them in LDS (filled from the device copy *cp) and the cost half reads them row by row where it uses
@@ -148,7 +153,25 @@ k_linearize(ModelConsts<S> c, const ModelConsts<S> *__restrict__ cp, BatchState 
 #pragma unroll
       for (int k = 0; k < 9; ++k) H[k] = at(cxx(k / 3, k % 3));
     };
-    if (add_obstacles((const S *)lin_obstacle_lds(), pack_obstacles(mod...).count, pt, cost, g, H, load)) {
+    bool any;
+    if constexpr (POBS) {
+      const ProblemObstacles &po = pack_problem_obstacles(mod...);
+      // the problem's row (a slot whose trajectory has left, orig = -1, reads nothing), its count, and the wavefront's largest count over
+      // the lanes still here: seven ballots, a scalar loop bound (count <= K <= OB_MAX = 64)
+      const long row = po.by_orig ? (long)st.orig[b] : (long)st.row0 + b;
+      const int cnt = row >= 0 ? po.counts[row] : 0;
+      int jend = 0;
+#pragma unroll
+      for (int bit = OB_MAX; bit > 0; bit >>= 1)
+        if (__ballot(cnt >= jend + bit) != 0ull) jend += bit;
+      any = false;
+      S R[9];
+      add_shared_spheres((const S *)lin_obstacle_lds(), po.shared.count, pt, cost, g, H, R, any, load);
+      add_problem_spheres(po.tab, po.K, row, cnt, jend, (double)i * c.dt, pt, cost, g, H, R, any, load);
+    } else {
+      any = add_obstacles((const S *)lin_obstacle_lds(), pack_obstacles(mod...).count, pt, cost, g, H, load);
+    }
+    if (any) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) at(L.off_g + k) = g[k];
 #pragma unroll

@@ -76,6 +76,7 @@ struct RouteInputs {
   qilqr_device_config dev{};  // force_general, single_wave_rollout, streams, persistent, compaction, round_launch, rounds_per_launch
   int num_cus = 256;
   int hw_queues = 4;  // hardware queues of the process (GPU_MAX_HW_QUEUES as the runtime read it)
+  bool problem_obstacles = false;  // per-problem spheres (qilqr_set_batch_obstacles): `obstacles` is set beside it, k_linearize takes their form
 };
 // What of the call itself the choice reads
 struct CallFacts {
@@ -88,6 +89,7 @@ struct CallFacts {
 // the extension arguments a kernel family receives
 struct ExtArgs {
   bool limits = false, models = false, obstacles = false;
+  bool problem_obstacles = false;  // (k_linearize) the form that carries the per-problem spheres beside the shared ones
 };
 
 struct Route {
@@ -184,7 +186,7 @@ inline Route plan_route(const RouteInputs &in, long B, const CallFacts &call) {
   // worth more than 1 % of k_linearize.)  The Runge-Kutta records hold a dense M at their head and have no such kind.
   r.lin_kind = (in.integrator == 0 && in.layout_kind == 2 && in.q_diag && !in.f32) ? 3 : in.layout_kind;
   r.backward_ext = r.rollout_ext = ExtArgs{in.limited, in.modeled, false};
-  r.linearize_ext = ExtArgs{false, in.modeled, in.obstacles};
+  r.linearize_ext = ExtArgs{false, in.modeled, in.obstacles, in.problem_obstacles};
   // k_backward_rollout (round_kernels.h): the backward pass and the rollout of a round in one launch, when every block of four
   // trajectories has a CU to itself (the rollout's register budget allows one block per CU) and the round's kernels are the
   // fused k_backward4 and k_rollout16 anyway.  qilqr_device_config.round_launch = 1 keeps them apart (A/B).

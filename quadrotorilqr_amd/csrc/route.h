@@ -1,7 +1,8 @@
 // route.h -- which kernels a call of B problems on a handle takes: ONE pure decision from the handle's inputs and the call's own facts
-// (plan_route), and the helpers for the choices that depend on counts the host learns while the call runs.  ilqr_capi.hip plans the route
-// once per call (begin_batch) and its launch helpers read it; qilqr_describe renders it.  Host code only, no HIP: tests/test_route_cpu.py
-// builds it with g++ and checks it against a table of the choices.
+// (plan_route), the helpers for the choices that depend on counts the host learns while the call runs, and the rule that says which
+// k_linearize instantiations exist (lin_instantiated).  The host side plans the route once per call (begin_batch, host/launches.h) and
+// its launch helpers read it; launch_linearize instantiates exactly the keys the rule admits; qilqr_describe renders the route.  Host code
+// only, no HIP: tests/test_route_cpu.py builds it with g++ and checks it against a table of the choices and a list of the admitted keys.
 #pragma once
 
 #include <algorithm>
@@ -285,5 +286,25 @@ inline TailFuse tail_fuse(const Route &r, bool compacting, int nparts) {
   }
   return t;
 }
+
+// ---- the instantiations of k_linearize (linearize_kernels.h): the record kind, the integrator, the placement of the records, the storage
+// precision and the extension argument that rides behind the common ones, as one key.  launch_linearize (host/launches.h) walks the key
+// space at compile time and instantiates the kernel for the keys lin_instantiated admits, and for no other.
+enum { LIN_PLAIN, LIN_MODELS, LIN_OBSTACLES, LIN_BOTH, LIN_PROBLEM = 4 };  // (ext: bits; LIN_PROBLEM rides on LIN_OBSTACLES)
+constexpr int LIN_KEYS = 256;
+constexpr int lin_key(int lk, int integ, bool tiled, bool f32, int ext) { return lk + 4 * integ + 8 * tiled + 16 * f32 + 32 * ext; }
+// Every instantiation the routes take: the extensions are fp64 and plain-placed but for the obstacles' tiled records (the symmetric kinds),
+// the Runge-Kutta records (integ = 1) are plain and have no diagonal kind.  (The placement of the records was chosen with the call's backward
+// kernel: Route::tiled.)
+constexpr bool lin_instantiated(int lk, int integ, bool tiled, bool f32, int ext) {
+  const bool models = ext & LIN_MODELS, obstacles = ext & LIN_OBSTACLES, problem = ext & LIN_PROBLEM;
+  if (problem && !obstacles) return false;                              // the per-problem spheres are a form of the obstacle argument
+  if (f32 && (lk == 3 || integ == 1 || ext != LIN_PLAIN)) return false;  // the mixed mode has no diagonal kind, and the extensions are fp64
+  if (integ == 1 && (tiled || lk == 3)) return false;                   // Runge-Kutta records are plain and have no diagonal kind
+  if (tiled && models) return false;                                    // models take the one-wavefront backward kernel: plain records
+  if (tiled && obstacles && lk == 0) return false;                      // tiled obstacle forms for the symmetric kinds only
+  return lk >= 0 && lk <= 3 && (integ == 0 || integ == 1) && ext >= 0 && ext < 8;
+}
+constexpr bool lin_instantiated(int key) { return lin_instantiated(key & 3, (key >> 2) & 1, (key >> 3) & 1, (key >> 4) & 1, key >> 5); }
 
 }  // namespace qilqr

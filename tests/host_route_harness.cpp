@@ -1,5 +1,6 @@
 // Host build of quadrotorilqr_amd/csrc/route.h for tests/test_route_cpu.py: one row of tests/golden/routes.json's inputs in, the
-// route's choices out, in the table's encoding.  Test scaffolding only.
+// route's choices out, in the table's encoding; and the keys of the k_linearize instantiations the rule admits (hr_lin_keys), for
+// tests/golden/linearize_keys.json.  Test scaffolding only.
 #include "../quadrotorilqr_amd/csrc/route.h"
 
 using namespace qilqr;
@@ -77,4 +78,25 @@ extern "C" int hr_route(const long *in, long *out) {
     *o++ = round_form(r, true, false, (unsigned)seen, B).six;
   }
   return (int)(o - out);
+}
+
+// Every key of the key space that lin_instantiated admits, as rows of {lin_kind, integrator, tiled, f32, ext} in key order; returns the
+// number of rows (cap rows are written), or -1 when the rule by key and the rule by fields disagree or a key leaves the key space.
+extern "C" int hr_lin_keys(long *out, int cap) {
+  int rows = 0;
+  for (int ext = 0; ext < 8; ++ext)
+    for (int f32 = 0; f32 < 2; ++f32)
+      for (int tiled = 0; tiled < 2; ++tiled)
+        for (int integ = 0; integ < 2; ++integ)
+          for (int lk = 0; lk < 4; ++lk) {
+            const int key = lin_key(lk, integ, tiled != 0, f32 != 0, ext);
+            if (key < 0 || key >= LIN_KEYS || lin_instantiated(key) != lin_instantiated(lk, integ, tiled != 0, f32 != 0, ext)) return -1;
+            if (!lin_instantiated(key)) continue;
+            if (rows < cap) {
+              const long row[5] = {lk, integ, tiled, f32, ext};
+              for (int q = 0; q < 5; ++q) out[5 * rows + q] = row[q];
+            }
+            ++rows;
+          }
+  return rows;
 }

@@ -1,7 +1,9 @@
 """The kernel choices of a call (quadrotorilqr_amd/csrc/route.h), built for the host with g++ and checked against
 tests/golden/routes.json: the choices the code made before they were gathered into plan_route, recorded over handles with each
 extension alone and combined, the mixed mode, general weights, the Runge-Kutta extension, the device configuration's A/B fields, the
-call's own facts and batch sizes from 1 to 65536, with the run-time choices at a few live counts."""
+call's own facts and batch sizes from 1 to 65536, with the run-time choices at a few live counts.  The rule that says which k_linearize
+instantiations exist (lin_instantiated) is checked against tests/golden/linearize_keys.json: the 58 keys of the hand-written dispatch it
+replaced, extracted from that dispatch's case lines."""
 import ctypes as C
 import json
 import os
@@ -23,6 +25,7 @@ def hr():
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-o", so, src])
     lib = C.CDLL(so)
     lib.hr_route.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    lib.hr_lin_keys.argtypes = [C.POINTER(C.c_long), C.c_int]
     return lib
 
 
@@ -78,3 +81,17 @@ def test_two_streams_at_1024_run_without_compaction(hr, golden):
     hr.hr_route(inp.ctypes.data_as(C.POINTER(C.c_long)), out.ctypes.data_as(C.POINTER(C.c_long)))
     got = dict(zip(golden["outputs"], out.tolist()))
     assert got["combined"] == 1 and got["parts"] == 2 and got["compact"] == 0 and got["tail_kinds"] == 0
+
+
+def test_linearize_instantiations_are_the_recorded_ones(hr):
+    """lin_instantiated admits exactly the recorded keys over the whole key space (4 kinds x 2 integrators x 2 placements x 2 precisions
+    x 8 extension forms): an instantiation added or lost by a change of the rule shows here, by name."""
+    with open(os.path.join(HERE, "golden", "linearize_keys.json")) as f:
+        want = json.load(f)
+    assert want["columns"] == ["lin_kind", "integrator", "tiled", "f32", "ext"] and len(want["rows"]) == 58
+    out = np.zeros((256, 5), dtype=np.int64)
+    n = hr.hr_lin_keys(out.ctypes.data_as(C.POINTER(C.c_long)), len(out))
+    assert 0 <= n <= len(out), n
+    got, exp = set(map(tuple, out[:n].tolist())), set(map(tuple, want["rows"]))
+    assert len(exp) == 58
+    assert got == exp, {"admitted but not recorded": sorted(got - exp), "recorded but not admitted": sorted(exp - got)}

@@ -355,6 +355,27 @@ int qilqr_set_obstacles(qilqr_solver *s, const double *spheres, int32_t count);
 #define QILQR_OBSTACLE_WORDS 8
 int qilqr_set_batch_obstacles(qilqr_solver *s, const double *spheres, const int32_t *counts, int32_t B, int32_t K);
 
+/* Per-knot state weights -- an EXTENSION: Qs is n_knots x 12 x 12 doubles (row-major, tangent order [rho, theta, dv, dw]), and from this
+ * call on knot i (0-based; the last knot has a cost like every other, ilqr.hh:89-95) of every problem takes Qs[i] wherever the handle's Q
+ * stood: the knot cost, C_x and C_xx.  A terminal weight ("be at this pose at the end": Q_f >> Q at the last knot) and waypoints (a large
+ * weight at a few knots, little or none between them) are schedules.  R, the desired trajectory, the model, dt and the options stay the
+ * handle's.  The index is the absolute knot index, as for the desired trajectory (cost.hh:39-40): a call with n < n_knots uses the first n
+ * matrices, a call with n > n_knots is refused with QILQR_ERR_LENGTH_MISMATCH.  The schedule is shared by every problem of the handle and
+ * used by every entry point that evaluates or differentiates the cost (qilqr_solve, qilqr_solve_batch[_device], qilqr_cost_trajectory,
+ * qilqr_backwards_pass, qilqr_line_search, and so qilqr_cost_history); qilqr_forward_sim evaluates no cost and is unaffected.
+ * While a schedule is set the handle takes the route of non-symmetric weights whatever its own Q is: dense knot records, in which all of
+ * C_xx travels, the one-wavefront backward kernel and three launches per round (qilqr_describe says so) -- in its symmetric-weight form
+ * when R and every Qs[i] are bit-exactly symmetric and force_general != 1, in the reference's own forms otherwise.  Definiteness is not
+ * checked (the handle's Q is not checked either): the symmetric-weight form factors Q_uu = 2 R + J_u^T V_xx J_u by an UNPIVOTED LDL^T and
+ * needs it positive definite, which holds for positive semi-definite Qs[i] and positive definite R.  Composes with either integrator,
+ * restarts, thrust limits (which need every Qs[i] symmetric), per-problem models, both sphere tables, per-problem desired trajectories,
+ * sub-batch streams, compaction = 1 and sharding.  The setter copies, uploads once, and waits for the handle's stream.
+ * QILQR_ERR_INVALID_ARG for a non-finite entry (qilqr_last_error names the first bad knot, row and column), n_knots < 1 with Qs given,
+ * a mixed-precision handle (precision = 1), a change that would leave thrust limits on non-symmetric weights (a non-symmetric Qs[i], or
+ * clearing a schedule that stands in for a non-symmetric Q: clear the limits first), and, while a schedule is set, a solve with
+ * persistent = 1.  Qs = NULL with n_knots = 0 clears: every result is then bit for bit the handle's without a schedule. */
+int qilqr_set_state_weight_schedule(qilqr_solver *s, const double *Qs, int32_t n_knots);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -449,6 +470,11 @@ int qilqr_sharded_set_obstacles(qilqr_sharded *h, const double *spheres, int32_t
  * sharded solves refuse another B.  The whole batch is checked first (the index in an error is the batch's); a failure leaves every
  * shard cleared.  NULL, NULL, 0, 0 clears. */
 int qilqr_sharded_set_batch_obstacles(qilqr_sharded *h, const double *spheres, const int32_t *counts, int32_t B, int32_t K);
+
+/* qilqr_set_state_weight_schedule on every shard's solver (the same schedule for the whole batch); checked once first, and any failure
+ * leaves every shard without a schedule -- but for a shard whose own setter refuses the clear (thrust limits set on that shard's solver
+ * over a non-symmetric Q, which only a symmetric schedule makes possible): it keeps the schedule it had.  NULL, 0 clears it. */
+int qilqr_sharded_set_state_weight_schedule(qilqr_sharded *h, const double *Qs, int32_t n_knots);
 const char *qilqr_sharded_transport(qilqr_sharded *h);
 int qilqr_solve_batch_sharded_device(qilqr_sharded *h, const double *init, const double *desired_batch, int32_t B, int32_t n,
                                      int32_t root, double *d_out_traj, double *d_out_cost, int32_t *d_out_status,
@@ -479,8 +505,9 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
 /* ABI version of this header: 7 (qilqr_device_config grew by round_launch, rounds_per_launch, fuse_in_flight, dense_weights -- the
  * switches that were environment variables -- and the *_sized entry points carry the caller's structure size; version 6 added
  * `compaction`).  qilqr_set_control_limits, QILQR_STATUS_QP_FAILED, qilqr_set_batch_models, qilqr_sharded_set_batch_models,
- * qilqr_set_obstacles, qilqr_sharded_set_obstacles, QILQR_MAX_OBSTACLES, qilqr_set_batch_obstacles, qilqr_sharded_set_batch_obstacles
- * and QILQR_OBSTACLE_WORDS were added within version 7: no structure changed. */
+ * qilqr_set_obstacles, qilqr_sharded_set_obstacles, QILQR_MAX_OBSTACLES, qilqr_set_batch_obstacles, qilqr_sharded_set_batch_obstacles,
+ * QILQR_OBSTACLE_WORDS, qilqr_set_state_weight_schedule and qilqr_sharded_set_state_weight_schedule were added within version 7: no
+ * structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

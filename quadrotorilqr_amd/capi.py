@@ -42,6 +42,7 @@ EXPORTS = (
     "qilqr_line_search", "qilqr_cost_history", "qilqr_profile_reset", "qilqr_profile_get", "qilqr_profile_mode", "qilqr_set_regularisation",
     "qilqr_set_integrator", "qilqr_set_control_limits", "qilqr_set_batch_models", "qilqr_sharded_set_batch_models",
     "qilqr_set_obstacles", "qilqr_sharded_set_obstacles", "qilqr_set_batch_obstacles", "qilqr_sharded_set_batch_obstacles",
+    "qilqr_set_state_weight_schedule", "qilqr_sharded_set_state_weight_schedule",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -109,6 +110,8 @@ def load():
         lib.qilqr_sharded_set_obstacles.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
         for f in (lib.qilqr_set_batch_obstacles, lib.qilqr_sharded_set_batch_obstacles):
             f.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32, C.c_int32]
+        for f in (lib.qilqr_set_state_weight_schedule, lib.qilqr_sharded_set_state_weight_schedule):
+            f.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
         _lib = lib
     return _lib
 
@@ -238,6 +241,15 @@ def batch_obstacle_arrays(spheres, counts=None):
             raise TypeError(f"batch obstacles: counts must be {arr.shape[0]} integers, one per problem; got {counts.dtype} {counts.shape}")
         counts = np.ascontiguousarray(counts, dtype=np.int32)
     return arr, counts
+
+
+def schedule_array(Qs):
+    """(n, 12, 12) float64 state weights for qilqr_set_state_weight_schedule (the library checks the values)"""
+    arr = _d(Qs)
+    if arr.ndim != 3 or arr.shape[1:] != (12, 12) or arr.shape[0] == 0:
+        raise TypeError(f"state-weight schedule: an (n, 12, 12) array of per-knot Q, n >= 1; got shape {arr.shape} "
+                        "(clear_state_weight_schedule() switches it off)")
+    return arr
 
 
 def _raise_models(rc):
@@ -523,6 +535,20 @@ class QuadrotorILQRBatch:
         if rc:
             _raise(rc)
 
+    def set_state_weight_schedule(self, Qs):
+        """Per-knot state weights (an extension): `Qs` is an (n, 12, 12) array and knot i of every problem takes Qs[i] for Q -- terminal
+        and waypoint costs (problems.terminal_schedule, problems.waypoint_schedule); see qilqr_set_state_weight_schedule in
+        include/quadrotor_ilqr.h.  clear_state_weight_schedule() switches it off again."""
+        arr = schedule_array(Qs)
+        rc = load().qilqr_set_state_weight_schedule(self._h, _p(arr), C.c_int32(len(arr)))
+        if rc != OK:
+            _raise(rc)
+
+    def clear_state_weight_schedule(self):
+        rc = load().qilqr_set_state_weight_schedule(self._h, None, C.c_int32(0))
+        if rc != OK:
+            _raise(rc)
+
     def profile_get(self):
         p = Profile()
         rc = load().qilqr_profile_get(self._h, C.byref(p))
@@ -629,6 +655,18 @@ class QuadrotorILQRSharded:
     def clear_batch_obstacles(self):
         rc = load().qilqr_sharded_set_batch_obstacles(self._h, None, None, C.c_int32(0), C.c_int32(0))
         if rc:
+            _raise(rc)
+
+    def set_state_weight_schedule(self, Qs):
+        """QuadrotorILQRBatch.set_state_weight_schedule on every shard's solver (qilqr_sharded_set_state_weight_schedule)"""
+        arr = schedule_array(Qs)
+        rc = load().qilqr_sharded_set_state_weight_schedule(self._h, _p(arr), C.c_int32(len(arr)))
+        if rc != OK:
+            _raise(rc)
+
+    def clear_state_weight_schedule(self):
+        rc = load().qilqr_sharded_set_state_weight_schedule(self._h, None, C.c_int32(0))
+        if rc != OK:
             _raise(rc)
 
     def clear_control_limits(self):

@@ -1,5 +1,5 @@
 // host/api_handle.h -- the C ABI of a handle: create and destroy, options, profiles, regularisation, and the setters of the extensions
-// (integrator, control limits, per-problem models, obstacles) with the checks of what they are given.  Part of ilqr_capi.hip's
+// (integrator, control limits, per-problem models, obstacles, the state-weight schedule) with the checks of what they are given.  Part of ilqr_capi.hip's
 // translation unit.
 #pragma once
 
@@ -87,6 +87,11 @@ int qilqr_create_sized(const qilqr_model *model, const double *Q, const double *
         if (i != k) diag = diag && (Q[i * 12 + k] == 0.0);
     s->q_diag = diag && dc.dense_weights == 0;  // (qilqr_device_config.dense_weights: A/B and the bit-identity test)
   }
+  // (what a cleared state-weight schedule restores)
+  s->own_symmetric = s->symmetric;
+  s->own_q_diag = s->q_diag;
+  s->own_layout_sym = s->layout.sym != 0;
+  s->own_layout_ur0 = s->layout.ur_zero != 0;
   s->n_desired = n_desired;
 
   hipError_t e = hipSetDevice(s->device);
@@ -168,6 +173,7 @@ void qilqr_destroy(qilqr_solver *s) {
   if (s->d_obstacles) (void)hipFree(s->d_obstacles);
   if (s->d_pobs) (void)hipFree(s->d_pobs);
   if (s->d_pobs_counts) (void)hipFree(s->d_pobs_counts);
+  if (s->d_qsched) (void)hipFree(s->d_qsched);
   if (s->d_consts) (void)hipFree(s->d_consts);
   if (s->h_counters) (void)hipHostFree(s->h_counters);
   if (s->h_active) (void)hipHostFree(s->h_active);
@@ -267,7 +273,7 @@ int qilqr_set_control_limits(qilqr_solver *s, const double *lo, const double *hi
         return fail(QILQR_ERR_INVALID_ARG, "control limits: rotor " + std::to_string(a) + " needs lo < hi and no NaN");
     if (s->f32) return fail(QILQR_ERR_INVALID_ARG, "control limits need precision 0 (fp64)");
     if (!s->symmetric)
-      return fail(QILQR_ERR_INVALID_ARG, "control limits need exactly symmetric Q and R (and force_general != 1): the box form is the symmetric recursion");
+      return fail(QILQR_ERR_INVALID_ARG, "control limits need exactly symmetric Q and R (and force_general != 1; with a state-weight schedule, every Q_i): the box form is the symmetric recursion");
     // the QP needs a strictly convex Q_uu = 2 R + J_u^T V_xx J_u: R positive definite (Cholesky of 2 R)
     double L[16] = {0};
     bool pd = true;
@@ -427,6 +433,74 @@ int qilqr_set_batch_obstacles(qilqr_solver *s, const double *spheres, const int3
     s->pobs_K = K;
     s->pobs_max = kmax;
     s->pobs_moving = moving;
+  }
+  return QILQR_OK;
+}
+
+namespace {
+// qilqr_set_state_weight_schedule's checks of what it is given (schedule.h, sched_check) and of the handle, shared with the sharded setter;
+// *symmetric: every Q_i == Q_i^T exactly
+int check_state_weight_schedule(const qilqr_solver *s, const double *Qs, int32_t n_knots, bool *symmetric) {
+  SchedCheck e;
+  if (sched_check(Qs, n_knots, &e)) {
+    std::string at;
+    if (e.knot >= 0) at = " (knot " + std::to_string(e.knot) + ", row " + std::to_string(e.row) + ", column " + std::to_string(e.col) + ")";
+    return fail(QILQR_ERR_INVALID_ARG, std::string("state-weight schedule: ") + e.why + at);
+  }
+  *symmetric = e.symmetric;
+  if (!Qs) {
+    // (limits can be set on a handle whose own Q is not symmetric while a symmetric schedule stands in for it)
+    if (s->limited && !s->own_symmetric)
+      return fail(QILQR_ERR_INVALID_ARG, "state-weight schedule: control limits are set and the handle's own Q and R are not exactly symmetric: "
+                                         "clear the limits before the schedule");
+    return QILQR_OK;
+  }
+  if (s->f32)
+    return fail(QILQR_ERR_INVALID_ARG, "state-weight schedule: needs precision 0 (fp64): the mixed-precision kernels have one Q");
+  if (s->limited && !e.symmetric)
+    return fail(QILQR_ERR_INVALID_ARG, "state-weight schedule: control limits are set and a Q_i is not exactly symmetric: the box form is the "
+                                       "symmetric recursion");
+  return QILQR_OK;
+}
+}  // namespace
+
+int qilqr_set_state_weight_schedule(qilqr_solver *s, const double *Qs, int32_t n_knots) {
+  if (!s) return fail(QILQR_ERR_INVALID_ARG, "null solver");
+  bool qsym = true;
+  int rc = check_state_weight_schedule(s, Qs, n_knots, &qsym);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));  // (no launch of this handle still reads the table)
+  // the records change shape with the schedule (the dense kind 0 while it is set, the kind of the handle's Q otherwise): the workspace is
+  // rebuilt on the next call, as for qilqr_set_integrator
+  const bool had = s->n_sched > 0;
+  if (had || Qs) free_workspace(s);
+  s->n_sched = 0;
+  s->sched_symmetric = false;
+  s->st.q_sched = nullptr;
+  s->st.n_sched = 0;
+  if (s->d_qsched) (void)hipFree(s->d_qsched);
+  s->d_qsched = nullptr;
+  s->symmetric = s->own_symmetric;
+  s->q_diag = s->own_q_diag;
+  s->layout = make_layout(s->own_layout_sym, s->own_layout_ur0, s->integrator == 1);
+  if (Qs) {
+    const size_t words = (size_t)n_knots * SCHED_WORDS;
+    HIP_TRY(hipMalloc((void **)&s->d_qsched, sizeof(double) * words));
+    const hipError_t up = hipMemcpy(s->d_qsched, Qs, sizeof(double) * words, hipMemcpyHostToDevice);
+    if (up != hipSuccess) {  // (the handle stays cleared: no table is left behind for a later call to read)
+      (void)hipFree(s->d_qsched);
+      s->d_qsched = nullptr;
+      return fail(QILQR_ERR_HIP, std::string("qilqr_set_state_weight_schedule: hipMemcpy: ") + hipGetErrorString(up));
+    }
+    bool rsym = true;
+    for (int i = 0; i < 4; ++i)
+      for (int k = 0; k < i; ++k) rsym = rsym && (s->consts.R[i * 4 + k] == s->consts.R[k * 4 + i]);
+    s->n_sched = n_knots;
+    s->sched_symmetric = qsym;
+    s->symmetric = qsym && rsym && s->dev.force_general != 1;
+    s->q_diag = false;
+    s->layout = make_layout(false, false, s->integrator == 1);
   }
   return QILQR_OK;
 }

@@ -43,6 +43,11 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
          ", at most " + std::to_string(s->pobs_max) + " used per problem, " + (s->pobs_moving ? "some moving" : "none moving") +
          ", penalised in the knot cost by k_linearize (the rounds never take the kernels that linearise inside themselves)" +
          (B != s->pobs_B ? " (a call of B = " + std::to_string(B) + " problems is refused)" : std::string());
+  if (s->n_sched > 0)
+    t += "; state-weight schedule (extension): n_knots = " + std::to_string(s->n_sched) + ", " +
+         (s->sched_symmetric ? "every Q_i symmetric" : "not every Q_i symmetric") +
+         ", knot i takes Qs[i] for Q in the cost half of k_linearize; the route of non-symmetric weights (dense records of kind 0, the "
+         "one-wavefront backward kernel, three launches per round) whatever the handle's Q is";
   t += s->f32 ? "; mixed precision (fp32 storage and lane-local arithmetic, fp64 recursion and cost sums)" : "; fp64";
   t += "; backward: ";
   t += persistent ? "k_solve4 (one launch per solve)" : kind == BW_FUSED ? "k_backward4, fused matrix + gradient wavefronts" : kind == BW_FOUR ? "k_backward4, six wavefronts"

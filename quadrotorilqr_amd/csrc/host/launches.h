@@ -7,7 +7,7 @@ namespace {
 // what of the handle the route reads (models = false: a call that ignores the per-problem models, qilqr_cost_trajectory)
 RouteInputs route_inputs(const qilqr_solver *s, bool models = true) {
   return RouteInputs{s->symmetric, s->q_diag, layout_kind(s->layout), s->f32, s->integrator, s->limited, s->modeled && models,
-                     s->n_obstacles > 0 || s->pobs_B > 0, s->dev, s->num_cus, hw_queues(), s->pobs_B > 0};
+                     s->n_obstacles > 0 || s->pobs_B > 0, s->dev, s->num_cus, hw_queues(), s->pobs_B > 0, s->n_sched > 0};
 }
 // the entry point a call comes through: a batch solve, qilqr_solve, a stand-alone pass, or qilqr_cost_trajectory (which ignores the models:
 // the cost does not depend on the model, and a call of any B takes the handle's own route); E_SIM: qilqr_forward_sim, a pass that
@@ -23,6 +23,8 @@ int refuse(const qilqr_solver *s, long B, Entry call) {
       return fail(QILQR_ERR_INVALID_ARG, "obstacles: persistent = 1 (k_solve4) linearises without them; take the rounds (persistent = 0)");
     if (s->pobs_B > 0)
       return fail(QILQR_ERR_INVALID_ARG, "batch obstacles: persistent = 1 (k_solve4) linearises without them; take the rounds (persistent = 0)");
+    if (s->n_sched > 0)
+      return fail(QILQR_ERR_INVALID_ARG, "state-weight schedule: persistent = 1 (k_solve4) linearises with the handle's Q; take the rounds (persistent = 0)");
   }
   // per-problem spheres (qilqr_set_batch_obstacles): problem b reads row b, so every call that evaluates the cost is over the rows they were
   // set for (qilqr_solve: B = 1)
@@ -44,6 +46,10 @@ int begin_batch(qilqr_solver *s, long B, long n, const double *d_desired_batch, 
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
   if (!d_desired_batch && n > s->n_desired)
     return fail(QILQR_ERR_LENGTH_MISMATCH, "trajectory longer than desired trajectory");
+  // the schedule is indexed by the absolute knot, as the desired trajectory is (a pass that evaluates no cost reads neither)
+  if (call != E_SIM && s->n_sched > 0 && n > s->n_sched)
+    return fail(QILQR_ERR_LENGTH_MISMATCH, "trajectory longer than the state-weight schedule (" + std::to_string(n) + " knots, " +
+                                               std::to_string(s->n_sched) + " matrices)");
   int rc = refuse(s, B, call);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(s->device));
@@ -58,6 +64,8 @@ int begin_batch(qilqr_solver *s, long B, long n, const double *d_desired_batch, 
     s->st.desired = s->d_desired;
     s->st.desired_tiled = 0;
   }
+  s->st.q_sched = s->n_sched > 0 ? s->d_qsched : nullptr;  // (null without a schedule: k_linearize then fills Q from the handle's constants)
+  s->st.n_sched = s->n_sched;
   s->total_B = B;
   s->live_hint = 0;  // (nothing known yet: launch_backward takes the batch)
   const CallFacts facts{s->dev.sync_every, d_desired_batch != nullptr, s->st.cost_hist != nullptr, s->early_out != nullptr, 0.0 < s->params.max_iters};

@@ -408,6 +408,15 @@ int qilqr_sharded_set_batch_obstacles(qilqr_sharded *h, const double *spheres, c
   return rc;
 }
 
+int qilqr_sharded_set_state_weight_schedule(qilqr_sharded *h, const double *Qs, int32_t n_knots) {
+  if (!h || h->solvers.empty()) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  // (checked once, before any shard changes; every shard the whole schedule; any failure leaves every shard cleared)
+  bool qsym = true;
+  const int checked = check_state_weight_schedule(h->solvers[0], Qs, n_knots, &qsym);
+  return sharded_set(h, 0, [&](qilqr_solver *s, int32_t, int32_t) { return qilqr_set_state_weight_schedule(s, Qs, n_knots); },
+                     [](qilqr_solver *s) { return qilqr_set_state_weight_schedule(s, nullptr, 0); }, checked);
+}
+
 int qilqr_sharded_set_transport(qilqr_sharded *h, int32_t transport) {
   if (!h) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   if (transport != QILQR_TRANSPORT_AUTO && transport != QILQR_TRANSPORT_RCCL && transport != QILQR_TRANSPORT_PEER_COPY)

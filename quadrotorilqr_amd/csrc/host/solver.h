@@ -56,6 +56,13 @@ struct qilqr_solver {
   bool pobs_moving = false;        // ... whether any used sphere has v != 0
   double *d_pobs = nullptr;        // ... the table in device memory, bob_count(pobs_B, pobs_K) doubles (obstacles.h, bob_index)
   int *d_pobs_counts = nullptr;    // ... and the counts, int32[pobs_B]
+  // the state-weight schedule (qilqr_set_state_weight_schedule): knot i of every problem takes Qs[i] for Q.  While it is set, `symmetric`,
+  // `q_diag` and `layout` above are the schedule's (R and every Q_i symmetric; never diagonal; the dense kind 0) and the own_* fields keep
+  // what qilqr_create derived from the handle's Q and R, for the clear
+  int n_sched = 0;                 // ... its knots (0: none)
+  bool sched_symmetric = false;    // ... every Q_i == Q_i^T exactly
+  double *d_qsched = nullptr;      // ... the matrices in device memory, [n_sched][144]
+  bool own_symmetric = false, own_q_diag = false, own_layout_sym = false, own_layout_ur0 = false;
   ModelConsts<float> constsf;   // the model constants for the fp32 lane-local kernels
   // workspace
   long cap_B = 0, cap_n = 0;

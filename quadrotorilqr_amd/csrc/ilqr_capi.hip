@@ -29,6 +29,7 @@
 #include "host_model.h"
 #include "ilqr_kernels.h"
 #include "route.h"
+#include "schedule.h"
 
 using namespace qilqr;
 

@@ -73,6 +73,10 @@ struct BatchState {
   double *dbg_trajs, *dbg_cost;
   int *dbg_seen;
   int dbg_cap;
+  // the state-weight schedule (qilqr_set_state_weight_schedule): [n_sched][144], row-major, fp64; null when none is set.  Knot i of every
+  // problem takes q_sched + 144 i in place of the handle's Q (the cost half of k_linearize, and no other kernel)
+  int n_sched;
+  const double *q_sched;
 };
 
 __device__ __forceinline__ int *active_counter(const BatchState &st) {

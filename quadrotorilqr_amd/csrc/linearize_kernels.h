@@ -97,7 +97,16 @@ k_linearize(ModelConsts<S> c, const ModelConsts<S> *__restrict__ cp, BatchState 
   const long b = (rest / n) * 64 + lane;
   if (cost_half) {  // wave-uniform (per_half is a multiple of 64)
     const int wl = threadIdx.x & 63;
-    for (int k = wl; k < 160; k += 64) qr[k] = (k < 144) ? cp->Q[k] : cp->R[k - 144];
+    // Q: the handle's, or knot i's of the state-weight schedule (qilqr_set_state_weight_schedule; fp64 handles only).  i is the same in
+    // every lane of the wavefront, so the choice is one scalar select of the base pointer in front of the fill; R is always the handle's
+    // (Q and R are then two ranges, each read from its own base: no choice per element)
+    if constexpr (std::is_same<S, double>::value) {
+      const S *qsrc = st.q_sched ? st.q_sched + 144l * __builtin_amdgcn_readfirstlane(i) : cp->Q;
+      for (int k = wl; k < 144; k += 64) qr[k] = qsrc[k];
+      if (wl < 16) qr[144 + wl] = cp->R[wl];
+    } else {
+      for (int k = wl; k < 160; k += 64) qr[k] = (k < 144) ? cp->Q[k] : cp->R[k - 144];
+    }
     if constexpr (OBS) {
       const Obstacles &ob = pack_obstacles(mod...);
       double *ot = lin_obstacle_lds();

@@ -38,7 +38,8 @@ constexpr int MAX_PARTS = 8;  // sub-batch streams of a handle
 // 16384: 593k / 512k, 65536: 654k / 587k); the one-wavefront kernel stays for force_general = 2.
 // k_backward2 (a matrix and a gradient wavefront per trajectory) was the choice below 512 trajectories in rounds 1 and 2; it
 // wins nowhere by more than 2 % and lives in the diagnostics build (force_general = 3 there).
-// The Runge-Kutta extension, the thrust limits, the per-problem models and non-symmetric weights take the one-wavefront kernel at every size.
+// The Runge-Kutta extension, the thrust limits, the per-problem models, non-symmetric weights and a state-weight schedule take the
+// one-wavefront kernel at every size.
 #ifndef QILQR_GFAC_MIN_LIVE
 #define QILQR_GFAC_MIN_LIVE 3072
 #endif
@@ -78,6 +79,10 @@ struct RouteInputs {
   int num_cus = 256;
   int hw_queues = 4;  // hardware queues of the process (GPU_MAX_HW_QUEUES as the runtime read it)
   bool problem_obstacles = false;  // per-problem spheres (qilqr_set_batch_obstacles): `obstacles` is set beside it, k_linearize takes their form
+  // a state-weight schedule is set (qilqr_set_state_weight_schedule): the route of non-symmetric weights -- dense records of kind 0, in which
+  // all of C_xx travels, and the one-wavefront backward kernel, which reads no constant derived from Q -- whatever the handle's Q is;
+  // `symmetric` then says whether R and every Q_i are (k_backward<true> or the general kernel)
+  bool scheduled = false;
 };
 // What of the call itself the choice reads
 struct CallFacts {
@@ -119,7 +124,7 @@ struct Route {
 
 inline BackwardKind backward_kind(const RouteInputs &in, long load_B) {
   const int fg = in.dev.force_general;
-  if (in.integrator == 1 || !in.symmetric || in.limited || in.modeled) return BW_ONE;
+  if (in.integrator == 1 || !in.symmetric || in.limited || in.modeled || in.scheduled) return BW_ONE;
 #ifdef QILQR_WITH_BACKWARD2
   if (fg == 3) return BW_TWO;
 #endif
@@ -166,7 +171,7 @@ inline Route plan_route(const RouteInputs &in, long B, const CallFacts &call) {
   // linearising wavefronts.
   // So 0 selects the rounds; the persistent solve stays selectable and tested.
 #ifdef QILQR_WITH_SOLVE4
-  r.persistent = in.symmetric && d.persistent == 1 && in.integrator == 0 && !in.limited && !in.modeled && !in.obstacles;
+  r.persistent = in.symmetric && d.persistent == 1 && in.integrator == 0 && !in.limited && !in.modeled && !in.obstacles && !in.scheduled;
 #endif  // (otherwise k_solve4 is in the diagnostics build: qilqr_create refuses persistent = 1 here)
   r.backward = backward_kind(in, B);
   // The knot records are placed for their reader (se3_math.h, rec_base): tiled for the kernels that stage them through LDS
@@ -185,7 +190,8 @@ inline Route plan_route(const RouteInputs &in, long B, const CallFacts &call) {
   // mixed mode: there the two instantiations differ in the last fp32 bit of a third of the knot costs -- the compiler
   // contracts the single-precision expressions differently -- and "the same results whatever the weights' structure" is
   // worth more than 1 % of k_linearize.)  The Runge-Kutta records hold a dense M at their head and have no such kind.
-  r.lin_kind = (in.integrator == 0 && in.layout_kind == 2 && in.q_diag && !in.f32) ? 3 : in.layout_kind;
+  // A state-weight schedule: the dense kind whatever the handle's Q is (k_round and k_backward4 keep 2 Q_vv in a constant table).
+  r.lin_kind = in.scheduled ? 0 : (in.integrator == 0 && in.layout_kind == 2 && in.q_diag && !in.f32) ? 3 : in.layout_kind;
   r.backward_ext = r.rollout_ext = ExtArgs{in.limited, in.modeled, false};
   r.linearize_ext = ExtArgs{false, in.modeled, in.obstacles, in.problem_obstacles};
   // k_backward_rollout (round_kernels.h): the backward pass and the rollout of a round in one launch, when every block of four
@@ -201,7 +207,7 @@ inline Route plan_route(const RouteInputs &in, long B, const CallFacts &call) {
   // the two launches).  The round's counts go into the counter set of its parity; the launch publishes the round before it.
   // A handle with obstacles keeps the two launches as well: k_round linearises with linearize_cost alone (the same bits as
   // k_backward_rollout + k_linearize, round_kernels.h), and only k_linearize adds the penalties.
-  r.round_kernel = d.round_launch == 0 && !in.f32 && !in.obstacles;
+  r.round_kernel = d.round_launch == 0 && !in.f32 && !in.obstacles && !in.scheduled;  // (k_round fills Q from the handle's constants itself)
   // rounds per launch of k_round where a launch may hold several (qilqr_device_config.rounds_per_launch = 1, 2 or 4: A/B; 0 = 4)
   r.rounds_per_launch = (d.rounds_per_launch == 1 || d.rounds_per_launch == 2) ? d.rounds_per_launch : 4;
   // A batch of 1025 ... 4096 trajectories runs the same two kernels apart, with the compaction between them; once the running

@@ -160,6 +160,29 @@ def config1(horizon_s=10.0):
                 desired=desired, init=desired[None].copy())
 
 
+def terminal_schedule(Q, Q_f, n):
+    """(n, 12, 12) state weights for set_state_weight_schedule: Q at knots 0 .. n - 2 and Q_f at the last knot ("be at this pose at
+    the end": Q_f >> Q)."""
+    if n < 1:
+        raise ValueError("a schedule has at least one knot")
+    Qs = np.broadcast_to(np.asarray(Q, dtype=np.float64), (n, 12, 12)).copy()
+    Qs[n - 1] = np.asarray(Q_f, dtype=np.float64)
+    return Qs
+
+
+def waypoint_schedule(Q_between, Q_at, n, knots):
+    """(n, 12, 12) state weights for set_state_weight_schedule: Q_at at the knots listed in `knots` (0-based, below n) and Q_between at
+    every other one ("pass through these poses on the way")."""
+    if n < 1:
+        raise ValueError("a schedule has at least one knot")
+    Qs = np.broadcast_to(np.asarray(Q_between, dtype=np.float64), (n, 12, 12)).copy()
+    for i in knots:
+        if not 0 <= int(i) < n:
+            raise ValueError(f"waypoint knot {i} is outside 0 .. {n - 1}")
+        Qs[int(i)] = np.asarray(Q_at, dtype=np.float64)
+    return Qs
+
+
 def config5(B=4096, N=500, seed=5):
     """BASELINE.json configs[4]: long-horizon stress.  Two halves that need two solver handles
     (different model and desired trajectory): (a) model A hover with random starts -- well posed;

@@ -376,6 +376,51 @@ int qilqr_set_batch_obstacles(qilqr_solver *s, const double *spheres, const int3
  * persistent = 1.  Qs = NULL with n_knots = 0 clears: every result is then bit for bit the handle's without a schedule. */
 int qilqr_set_state_weight_schedule(qilqr_solver *s, const double *Qs, int32_t n_knots);
 
+/* Receding-horizon control -- an EXTENSION in two parts: a window into the handle's desired trajectory and schedule, and the step from
+ * one solve's plan to the next solve's initial trajectory.  At every control tick a caller drops the knots that have been flown, anchors
+ * knot 0 at the measured state, extends the end of the horizon and solves again (quadrotorilqr_amd/mpc.py does this on device buffers).
+ *
+ * Horizon start.  From this call on, knot i of every call of the handle takes desired[k0 + i] of the desired trajectory given at create
+ * and, wherever a state-weight schedule is read, Qs[k0 + i]: a mission of 1000 knots is flown with a 100-knot horizon on ONE handle, without
+ * a per-problem desired_batch (which also switches the compaction off).  A call of n knots needs n <= n_desired - k0 when no desired_batch
+ * is given and, where it evaluates the cost, n <= n_knots - k0 of the schedule: QILQR_ERR_LENGTH_MISMATCH otherwise.  A per-problem
+ * desired_batch is already the caller's window and is unaffected.  BOTH SPHERE TABLES ARE UNAFFECTED: a moving sphere's time stays i dt
+ * from the call's first knot, because that table is a prediction made at tick time (set it again at the tick, centres at their positions
+ * then).  The route, the records and every kernel are those of the handle without a start: the start is an offset of two pointers, and
+ * k0 = 0 restores the handle bit for bit.  Nothing is waited for.  QILQR_ERR_INVALID_ARG unless 0 <= k0 < n_desired, and k0 < n_knots
+ * while a schedule is set (0 is always accepted), and for a non-zero start on a mixed-precision handle (precision = 1); a refused call
+ * leaves the start that was in force.  The rule holds from the other side too: while a start is in force, qilqr_set_state_weight_schedule
+ * refuses a schedule with n_knots <= k0 (QILQR_ERR_INVALID_ARG, the handle keeps the schedule it had): lower the start first. */
+int qilqr_set_horizon_start(qilqr_solver *s, int32_t k0);
+
+/* The shift.  Arrays are plain B x n x 18 as everywhere; 0 <= steps <= n - 1.  Problem by problem:
+ *   kept knots     out[b, i] = traj[b, i + steps] for i < n - steps: all 18 words bit for bit, the time column included
+ *   tail           j = n - steps .. n - 1: the state of knot j is ONE DYNAMICS STEP from the state of output knot j - 1 under the control
+ *                  stored there (output knot n - 1 - steps is traj[b, n - 1] as given, its control included).  The step is the handle's:
+ *                  its dt, its integrator (qilqr_set_integrator) and models[b] while per-problem models are set, in the arithmetic of the
+ *                  solver's own rollout.  The control stored at a tail knot is traj[b, n - 1, 14:18] (QILQR_TAIL_HOLD) or mass g / 4 of
+ *                  the problem's model on every rotor (QILQR_TAIL_HOVER), clamped to the thrust limits while they are set.  Its time is
+ *                  traj[b, n - 1, 0] + k dt, k = j - (n - 1 - steps)
+ *   re-anchoring   with x0 (B x QILQR_STATE: words 1..13 of a knot -- t(3), q w,x,y,z, v_lin(3), v_ang(3)) words 1..13 of output knot 0
+ *                  are x0[b]; its time and control stay.  Nothing else is rolled again -- the tail starts from traj[b, n - 1] whatever x0
+ *                  is, and the solver's first closed-loop rollout starts from knot 0.  x0 = NULL: no re-anchoring
+ * The shift evaluates no cost: spheres, schedules and the horizon start play no part.  One launch (k_shift) reads traj and writes out.
+ * Both forms: QILQR_ERR_INVALID_ARG for a NULL traj or out, steps or tail out of range, a mixed-precision handle, another B than the
+ * per-problem models were set for, an array that is not 16-byte aligned, and an out that overlaps traj or x0 (the copy is parallel: in
+ * place is a race).  qilqr_shift_batch (host arrays) checks x0's quaternions as initial trajectories are checked
+ * (QILQR_ERR_BAD_QUATERNION, naming the problem) and returns when out is written.  qilqr_shift_batch_device (arrays in the memory of the
+ * handle's device) checks nothing on the device, ENQUEUES on the handle's stream (qilqr_stream) and returns WITHOUT draining it: the next
+ * solve on the handle is ordered behind it; work on any other stream that writes d_traj / d_x0 or reads d_out orders itself as for
+ * qilqr_solve_batch_device -- an event passed to qilqr_stream_wait_event before the call, or synchronise the stream (hipStreamSynchronize
+ * on qilqr_stream, or any draining call of the handle) before reading. */
+#define QILQR_STATE 13
+#define QILQR_TAIL_HOLD 0
+#define QILQR_TAIL_HOVER 1
+int qilqr_shift_batch_device(qilqr_solver *s, const double *d_traj, const double *d_x0, int32_t B, int32_t n, int32_t steps, int32_t tail,
+                             double *d_out);
+int qilqr_shift_batch(qilqr_solver *s, const double *traj, const double *x0, int32_t B, int32_t n, int32_t steps, int32_t tail,
+                      double *out);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -475,6 +520,10 @@ int qilqr_sharded_set_batch_obstacles(qilqr_sharded *h, const double *spheres, c
  * leaves every shard without a schedule -- but for a shard whose own setter refuses the clear (thrust limits set on that shard's solver
  * over a non-symmetric Q, which only a symmetric schedule makes possible): it keeps the schedule it had.  NULL, 0 clears it. */
 int qilqr_sharded_set_state_weight_schedule(qilqr_sharded *h, const double *Qs, int32_t n_knots);
+
+/* qilqr_set_horizon_start on every shard's solver (the same start for the whole batch); checked once first, all or none: a failure leaves
+ * every shard at start 0. */
+int qilqr_sharded_set_horizon_start(qilqr_sharded *h, int32_t k0);
 const char *qilqr_sharded_transport(qilqr_sharded *h);
 int qilqr_solve_batch_sharded_device(qilqr_sharded *h, const double *init, const double *desired_batch, int32_t B, int32_t n,
                                      int32_t root, double *d_out_traj, double *d_out_cost, int32_t *d_out_status,
@@ -506,8 +555,9 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * switches that were environment variables -- and the *_sized entry points carry the caller's structure size; version 6 added
  * `compaction`).  qilqr_set_control_limits, QILQR_STATUS_QP_FAILED, qilqr_set_batch_models, qilqr_sharded_set_batch_models,
  * qilqr_set_obstacles, qilqr_sharded_set_obstacles, QILQR_MAX_OBSTACLES, qilqr_set_batch_obstacles, qilqr_sharded_set_batch_obstacles,
- * QILQR_OBSTACLE_WORDS, qilqr_set_state_weight_schedule and qilqr_sharded_set_state_weight_schedule were added within version 7: no
- * structure changed. */
+ * QILQR_OBSTACLE_WORDS, qilqr_set_state_weight_schedule, qilqr_sharded_set_state_weight_schedule, qilqr_set_horizon_start,
+ * qilqr_sharded_set_horizon_start, qilqr_shift_batch, qilqr_shift_batch_device, QILQR_STATE, QILQR_TAIL_HOLD and QILQR_TAIL_HOVER were added
+ * within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

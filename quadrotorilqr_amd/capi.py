@@ -34,6 +34,8 @@ STATUS_LINE_SEARCH_FAILED = 3
 STATUS_QP_FAILED = 4  # extension: a knot's box QP broke down (set_control_limits)
 MAX_OBSTACLES = 64  # QILQR_MAX_OBSTACLES: spheres per handle (set_obstacles), and per problem (set_batch_obstacles)
 OBSTACLE_WORDS = 8  # QILQR_OBSTACLE_WORDS: {cx, cy, cz, vx, vy, vz, radius, weight} of a per-problem sphere (set_batch_obstacles)
+STATE = 13  # QILQR_STATE: words 1..13 of a knot, t(3), q w,x,y,z, v_lin(3), v_ang(3) (shift's x0)
+TAILS = {"hold": 0, "hover": 1}  # QILQR_TAIL_HOLD, QILQR_TAIL_HOVER: the control of the knots a shift appends
 
 # every symbol include/quadrotor_ilqr.h declares
 EXPORTS = (
@@ -43,6 +45,7 @@ EXPORTS = (
     "qilqr_set_integrator", "qilqr_set_control_limits", "qilqr_set_batch_models", "qilqr_sharded_set_batch_models",
     "qilqr_set_obstacles", "qilqr_sharded_set_obstacles", "qilqr_set_batch_obstacles", "qilqr_sharded_set_batch_obstacles",
     "qilqr_set_state_weight_schedule", "qilqr_sharded_set_state_weight_schedule",
+    "qilqr_set_horizon_start", "qilqr_sharded_set_horizon_start", "qilqr_shift_batch", "qilqr_shift_batch_device",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -112,12 +115,22 @@ def load():
             f.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32, C.c_int32]
         for f in (lib.qilqr_set_state_weight_schedule, lib.qilqr_sharded_set_state_weight_schedule):
             f.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
+        for f in (lib.qilqr_set_horizon_start, lib.qilqr_sharded_set_horizon_start):
+            f.argtypes = [C.c_void_p, C.c_int32]
+        for f in (lib.qilqr_shift_batch, lib.qilqr_shift_batch_device):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         _lib = lib
     return _lib
 
 
 def _d(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _d16(a):
+    """_d, on a 16-byte boundary (a row of a larger array may start 8 bytes off one: copied)"""
+    a = _d(a)
+    return a if a.ctypes.data % 16 == 0 else a.copy()
 
 
 def _p(a):
@@ -250,6 +263,12 @@ def schedule_array(Qs):
         raise TypeError(f"state-weight schedule: an (n, 12, 12) array of per-knot Q, n >= 1; got shape {arr.shape} "
                         "(clear_state_weight_schedule() switches it off)")
     return arr
+
+
+def _tail(tail):
+    if tail not in TAILS:
+        raise TypeError(f"tail must be one of {sorted(TAILS)}, not {tail!r}")
+    return TAILS[tail]
 
 
 def _raise_models(rc):
@@ -549,6 +568,66 @@ class QuadrotorILQRBatch:
         if rc != OK:
             _raise(rc)
 
+    # ---- receding-horizon stepping
+    def set_horizon_start(self, k0):
+        """From this call on knot i of every call reads desired[k0 + i] of the handle's desired trajectory and Qs[k0 + i] of its
+        state-weight schedule (an extension; 0 restores the handle) -- see qilqr_set_horizon_start in include/quadrotor_ilqr.h."""
+        rc = load().qilqr_set_horizon_start(self._h, C.c_int32(int(k0)))
+        if rc:
+            _raise(rc)
+
+    def shift(self, traj, x0=None, steps=1, tail="hold"):
+        """qilqr_shift_batch, host arrays: the plan (B, n, 18) moved `steps` knots towards its start, its end extended by dynamics steps
+        under the held last control (tail='hold') or the hover thrust ('hover'), knot 0's state replaced by x0 (B, 13) when given.  Returns
+        the new (B, n, 18) array: the next solve's initial trajectory."""
+        traj = _d16(traj)
+        if traj.ndim != 3 or traj.shape[2] != KNOT:
+            raise TypeError("traj must be (B, n, 18)")
+        B, n = traj.shape[0], traj.shape[1]
+        if x0 is not None:
+            x0 = _d16(x0)
+            if x0.shape != (B, STATE):
+                raise TypeError(f"x0 must be ({B}, {STATE}): words 1..13 of a knot per problem")
+        out = np.zeros_like(traj)
+        vp = lambda a: C.c_void_p(0 if a is None else a.ctypes.data)
+        rc = load().qilqr_shift_batch(self._h, vp(traj), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(int(steps)), C.c_int32(_tail(tail)), vp(out))
+        if rc:
+            _raise(rc)
+        return out
+
+    def shift_device(self, traj, out, x0=None, steps=1, tail="hold", wait_current_stream=True):
+        """qilqr_shift_batch_device on torch tensors, checked like solve_batch_device: traj and out float64 (B, n, 18), x0 float64 (B, 13)
+        or None, on the solver's device, contiguous.  The launch is ENQUEUED on the solver's own stream -- behind whatever torch has
+        enqueued on its current stream (wait_current_stream) -- and this returns without waiting: a solve on this handle is ordered behind
+        it; torch work that reads `out` waits for the solver's stream first (any draining call of the handle, or an event)."""
+        import torch
+        if traj.dim() != 3 or traj.shape[2] != KNOT:
+            raise TypeError("traj must be (B, n, 18)")
+        B, n = int(traj.shape[0]), int(traj.shape[1])
+        dev_index = load().qilqr_device(self._h)
+        for t, name, shape in ((traj, "traj", (B, n, KNOT)), (out, "out", (B, n, KNOT)), (x0, "x0", (B, STATE))):
+            if t is None and name == "x0":
+                continue
+            if t is None or not t.is_cuda or t.device.index != dev_index:
+                raise TypeError(f"{name} must be a CUDA tensor on device {dev_index}")
+            if t.dtype != torch.float64:
+                raise TypeError(f"{name} must be {torch.float64}")
+            if tuple(t.shape) != shape:
+                raise TypeError(f"{name} must have shape {shape}, not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise TypeError(f"{name} must be contiguous")
+        tail = _tail(tail)
+        if wait_current_stream:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(traj.device))
+            rc = load().qilqr_stream_wait_event(self._h, C.c_void_p(ev.cuda_event))
+            if rc:
+                _raise(rc)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        rc = load().qilqr_shift_batch_device(self._h, vp(traj), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(int(steps)), C.c_int32(tail), vp(out))
+        if rc:
+            _raise(rc)
+
     def profile_get(self):
         p = Profile()
         rc = load().qilqr_profile_get(self._h, C.byref(p))
@@ -667,6 +746,12 @@ class QuadrotorILQRSharded:
     def clear_state_weight_schedule(self):
         rc = load().qilqr_sharded_set_state_weight_schedule(self._h, None, C.c_int32(0))
         if rc != OK:
+            _raise(rc)
+
+    def set_horizon_start(self, k0):
+        """QuadrotorILQRBatch.set_horizon_start on every shard's solver (qilqr_sharded_set_horizon_start: checked once, all or none)"""
+        rc = load().qilqr_sharded_set_horizon_start(self._h, C.c_int32(int(k0)))
+        if rc:
             _raise(rc)
 
     def clear_control_limits(self):

@@ -1,5 +1,5 @@
-// host/api_calls.h -- the C ABI of the computing calls on one handle: the batch solves, qilqr_solve, the four stand-alone passes and
-// the pinned host memory for their callers.  Part of ilqr_capi.hip's translation unit.
+// host/api_calls.h -- the C ABI of the computing calls on one handle: the batch solves, qilqr_solve, the four stand-alone passes, the
+// pinned host memory for their callers, and the receding-horizon shift (whose kernel is shift.hip's).  Part of ilqr_capi.hip's translation unit.
 #pragma once
 
 extern "C" {
@@ -291,5 +291,76 @@ int qilqr_line_search(qilqr_solver *s, const double *traj, const double *cost, c
   if (out_traj && (rc = download_tiled(s, out_traj, s->st.traj[0], s->st.traj[1], s->st.cur, 0, B, n, 18))) return rc;
   HIP_TRY(hipGetLastError());
   return device_error(s);
+}
+
+// ---- the step between two solves of a receding horizon: k_shift (shift_kernels.h, compiled by shift.hip) on the caller's arrays
+namespace {
+// what both forms refuse (the pointers are the caller's: host ones for qilqr_shift_batch, device ones for qilqr_shift_batch_device)
+int shift_refuse(const qilqr_solver *s, const double *traj, const double *x0, int32_t B, int32_t n, int32_t steps, int32_t tail,
+                 const double *out) {
+  if (!s || !traj || !out) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
+  if (steps < 0 || steps > n - 1)
+    return fail(QILQR_ERR_INVALID_ARG, "shift: steps must be 0 ... n - 1 (" + std::to_string(steps) + " with n = " + std::to_string(n) + ")");
+  if (tail != QILQR_TAIL_HOLD && tail != QILQR_TAIL_HOVER) return fail(QILQR_ERR_INVALID_ARG, "shift: tail must be QILQR_TAIL_HOLD or QILQR_TAIL_HOVER");
+  if (s->f32) return fail(QILQR_ERR_INVALID_ARG, "shift: needs precision 0 (fp64)");
+  if (s->modeled && B != s->models_B)
+    return fail(QILQR_ERR_INVALID_ARG, "batch models were set for B = " + std::to_string(s->models_B) + " problems; this shift has B = " +
+                                           std::to_string(B) + " (set them again, or clear them, for another batch)");
+  if (((uintptr_t)traj | (uintptr_t)out | (uintptr_t)x0) & 15) return fail(QILQR_ERR_INVALID_ARG, "shift: every array must be 16-byte aligned");
+  // the copy is parallel and every block reads only the input: an output that overlaps an input is a race
+  const char *i0 = (const char *)traj, *o0 = (const char *)out, *x = (const char *)x0;
+  const size_t tb = sizeof(double) * 18 * (size_t)B * n, xb = sizeof(double) * QILQR_STATE * (size_t)B;
+  if (i0 < o0 + tb && o0 < i0 + tb) return fail(QILQR_ERR_INVALID_ARG, "shift: the output overlaps the input (the shift does not work in place)");
+  if (x && x < o0 + tb && o0 < x + xb) return fail(QILQR_ERR_INVALID_ARG, "shift: the output overlaps x0");
+  return QILQR_OK;
+}
+int shift_enqueue(qilqr_solver *s, const double *d_traj, const double *d_x0, int32_t B, int32_t n, int32_t steps, int32_t tail, double *d_out) {
+  const ShiftLaunch call{d_traj, d_x0, d_out, B, n, steps, tail, s->integrator, s->limited ? &s->limits : nullptr, s->modeled ? s->d_models : nullptr};
+  const hipError_t e = launch_shift(s->stream, s->consts, call);
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_shift: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+}  // namespace
+
+static_assert(QILQR_STATE == 13 && QILQR_TAIL_HOLD == 0 && QILQR_TAIL_HOVER == 1, "shift_kernels.h and the C header agree on the state words and the tails");
+int qilqr_shift_batch_device(qilqr_solver *s, const double *d_traj, const double *d_x0, int32_t B, int32_t n, int32_t steps, int32_t tail,
+                             double *d_out) {
+  int rc = shift_refuse(s, d_traj, d_x0, B, n, steps, tail, d_out);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return shift_enqueue(s, d_traj, d_x0, B, n, steps, tail, d_out);  // (enqueued on the handle's stream; not waited for)
+}
+
+int qilqr_shift_batch(qilqr_solver *s, const double *traj, const double *x0, int32_t B, int32_t n, int32_t steps, int32_t tail, double *out) {
+  int rc = shift_refuse(s, traj, x0, B, n, steps, tail, out);
+  if (rc) return rc;
+  if (x0)  // as the initial trajectories are checked (manif's constructor check), naming the problem
+    for (long b = 0; b < B; ++b) {
+      const double *q = x0 + b * QILQR_STATE + 3;
+      const double nn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      if (!(std::fabs(nn - 1.0) <= 1e-10)) return fail(QILQR_ERR_BAD_QUATERNION, "x0: quaternion not normalized at problem " + std::to_string(b));
+    }
+  HIP_TRY(hipSetDevice(s->device));
+  struct Scratch {  // freed on every return path
+    double *p = nullptr;
+    ~Scratch() {
+      if (p) (void)hipFree(p);
+    }
+  } scratch;
+  const size_t cnt = 18 * (size_t)B * n, xcnt = (size_t)QILQR_STATE * B;  // (cnt is even: input, output and x0 each start on 16 bytes)
+  HIP_TRY(hipMalloc((void **)&scratch.p, sizeof(double) * (2 * cnt + xcnt)));
+  double *d_in = scratch.p, *d_out = d_in + cnt, *d_x0 = x0 ? d_out + cnt : nullptr;
+  HIP_TRY(hipMemcpyAsync(d_in, traj, sizeof(double) * cnt, hipMemcpyHostToDevice, s->stream));
+  if (x0) HIP_TRY(hipMemcpyAsync(d_x0, x0, sizeof(double) * QILQR_STATE * (size_t)B, hipMemcpyHostToDevice, s->stream));
+  hipError_t e = hipSuccess;
+  if ((rc = shift_enqueue(s, d_in, d_x0, B, n, steps, tail, d_out)) == QILQR_OK)
+    e = hipMemcpyAsync(out, d_out, sizeof(double) * cnt, hipMemcpyDeviceToHost, s->stream);
+  const hipError_t drained = hipStreamSynchronize(s->stream);  // (the copies read and write the caller's arrays, the kernel the scratch: finished before either goes)
+  if (rc) return rc;
+  if (e == hipSuccess) e = drained;
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("qilqr_shift_batch: ") + hipGetErrorString(e));
+  return QILQR_OK;
 }
 }  // extern "C"

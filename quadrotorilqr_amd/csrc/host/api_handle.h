@@ -1,5 +1,5 @@
 // host/api_handle.h -- the C ABI of a handle: create and destroy, options, profiles, regularisation, and the setters of the extensions
-// (integrator, control limits, per-problem models, obstacles, the state-weight schedule) with the checks of what they are given.  Part of ilqr_capi.hip's
+// (integrator, control limits, per-problem models, obstacles, the state-weight schedule, the horizon start) with the checks of what they are given.  Part of ilqr_capi.hip's
 // translation unit.
 #pragma once
 
@@ -457,6 +457,9 @@ int check_state_weight_schedule(const qilqr_solver *s, const double *Qs, int32_t
   }
   if (s->f32)
     return fail(QILQR_ERR_INVALID_ARG, "state-weight schedule: needs precision 0 (fp64): the mixed-precision kernels have one Q");
+  const char *why = nullptr;  // (qilqr_set_horizon_start keeps k0 < n_knots from its side)
+  if (horizon_schedule_check(s->k0, n_knots, &why))
+    return fail(QILQR_ERR_INVALID_ARG, std::string(why) + " (n_knots = " + std::to_string(n_knots) + ", horizon start " + std::to_string(s->k0) + ")");
   if (s->limited && !e.symmetric)
     return fail(QILQR_ERR_INVALID_ARG, "state-weight schedule: control limits are set and a Q_i is not exactly symmetric: the box form is the "
                                        "symmetric recursion");
@@ -502,6 +505,28 @@ int qilqr_set_state_weight_schedule(qilqr_solver *s, const double *Qs, int32_t n
     s->q_diag = false;
     s->layout = make_layout(false, false, s->integrator == 1);
   }
+  return QILQR_OK;
+}
+
+namespace {
+// qilqr_set_horizon_start's checks (horizon.h, horizon_start_check) and of the handle, shared with the sharded setter
+int check_horizon_start(const qilqr_solver *s, int32_t k0) {
+  const char *why = nullptr;
+  if (horizon_start_check(k0, s->n_desired, s->n_sched, &why))
+    return fail(QILQR_ERR_INVALID_ARG, std::string(why) + " (k0 = " + std::to_string(k0) + ", desired trajectory of " + std::to_string(s->n_desired) +
+                                           " knots" + (s->n_sched > 0 ? ", schedule of " + std::to_string(s->n_sched) : std::string()) + ")");
+  // (the fp32 shared desired trajectory has 72-byte rows: an odd start would move the row base off 16 bytes)
+  if (k0 != 0 && s->f32) return fail(QILQR_ERR_INVALID_ARG, "horizon start: needs precision 0 (fp64)");
+  return QILQR_OK;
+}
+}  // namespace
+
+int qilqr_set_horizon_start(qilqr_solver *s, int32_t k0) {
+  if (!s) return fail(QILQR_ERR_INVALID_ARG, "null solver");
+  const int rc = check_horizon_start(s, k0);
+  if (rc) return rc;
+  // (begin_batch reads it when the next call starts; launches in flight have their pointers already: nothing to wait for)
+  s->k0 = k0;
   return QILQR_OK;
 }
 

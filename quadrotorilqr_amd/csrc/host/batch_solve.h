@@ -516,8 +516,8 @@ int solve_batch_device_impl(qilqr_solver *s, const double *d_init, const double 
 int solve_batch_staged(qilqr_solver *s, const double *init, const double *desired_batch, int32_t B, int32_t n) {
   if (!s || !init) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
-  if (!desired_batch && n > s->n_desired)
-    return fail(QILQR_ERR_LENGTH_MISMATCH, "trajectory longer than desired trajectory");
+  const char *why = nullptr;  // (the desired trajectory's length from the horizon start on; begin_batch checks the schedule's)
+  if (horizon_window_check(n, s->k0, s->n_desired, 0, !desired_batch, false, &why)) return fail(QILQR_ERR_LENGTH_MISMATCH, why);
   int rc;
   if ((rc = refuse(s, B, E_BATCH))) return rc;  // (before anything is enqueued)
   HIP_TRY(hipSetDevice(s->device));

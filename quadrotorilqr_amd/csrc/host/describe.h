@@ -48,6 +48,10 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
          (s->sched_symmetric ? "every Q_i symmetric" : "not every Q_i symmetric") +
          ", knot i takes Qs[i] for Q in the cost half of k_linearize; the route of non-symmetric weights (dense records of kind 0, the "
          "one-wavefront backward kernel, three launches per round) whatever the handle's Q is";
+  if (s->k0 != 0)
+    t += "; horizon start (extension): knot i of a call reads desired[" + std::to_string(s->k0) + " + i] of the handle's desired trajectory" +
+         (s->n_sched > 0 ? " and Qs[" + std::to_string(s->k0) + " + i] of the schedule" : std::string()) +
+         " (a per-problem desired_batch and both sphere tables are the call's own)";
   t += s->f32 ? "; mixed precision (fp32 storage and lane-local arithmetic, fp64 recursion and cost sums)" : "; fp64";
   t += "; backward: ";
   t += persistent ? "k_solve4 (one launch per solve)" : kind == BW_FUSED ? "k_backward4, fused matrix + gradient wavefronts" : kind == BW_FOUR ? "k_backward4, six wavefronts"

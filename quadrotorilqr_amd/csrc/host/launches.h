@@ -40,16 +40,21 @@ int refuse(const qilqr_solver *s, long B, Entry call) {
                                            std::to_string(B) + " (set them again, or clear them, for another batch)");
   return QILQR_OK;
 }
+// ", horizon start k0" for the messages of a handle that has one
+std::string horizon_text(const qilqr_solver *s) { return s->k0 ? ", horizon start " + std::to_string(s->k0) : std::string(); }
 // bind the desired trajectory (shared, or per problem: plain device array, re-tiled here), plan the call's route and reset the buffer
 // selectors
 int begin_batch(qilqr_solver *s, long B, long n, const double *d_desired_batch, Entry call) {
   if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
-  if (!d_desired_batch && n > s->n_desired)
-    return fail(QILQR_ERR_LENGTH_MISMATCH, "trajectory longer than desired trajectory");
-  // the schedule is indexed by the absolute knot, as the desired trajectory is (a pass that evaluates no cost reads neither)
-  if (call != E_SIM && s->n_sched > 0 && n > s->n_sched)
-    return fail(QILQR_ERR_LENGTH_MISMATCH, "trajectory longer than the state-weight schedule (" + std::to_string(n) + " knots, " +
-                                               std::to_string(s->n_sched) + " matrices)");
+  // the desired trajectory and the schedule are indexed by the absolute knot, from the horizon start on (horizon.h; a pass that evaluates
+  // no cost does not read the schedule)
+  const char *why = nullptr;
+  const int window = horizon_window_check(n, s->k0, s->n_desired, s->n_sched, !d_desired_batch, call != E_SIM, &why);
+  if (window == HZ_LENGTH_SCHEDULE)
+    return fail(QILQR_ERR_LENGTH_MISMATCH, std::string(why) + " (" + std::to_string(n) + " knots, " + std::to_string(s->n_sched) + " matrices" +
+                                               horizon_text(s) + ")");
+  if (window != HZ_OK)
+    return fail(QILQR_ERR_LENGTH_MISMATCH, why + (s->k0 ? " (" + std::to_string(s->n_desired) + " knots" + horizon_text(s) + ")" : std::string()));
   int rc = refuse(s, B, call);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(s->device));
@@ -61,11 +66,15 @@ int begin_batch(qilqr_solver *s, long B, long n, const double *d_desired_batch, 
     s->st.desired = s->desired_tiled;
     s->st.desired_tiled = 1;
   } else {
-    s->st.desired = s->d_desired;
+    // the shared one from the horizon start on: plain [n_desired][18] rows (k0 < n_desired, or 0: the setter; fp64 whenever k0 != 0: the
+    // setter refuses the mixed mode)
+    s->st.desired = (const char *)s->d_desired + (size_t)s->k0 * 18 * (s->f32 ? sizeof(float) : sizeof(double));
     s->st.desired_tiled = 0;
   }
-  s->st.q_sched = s->n_sched > 0 ? s->d_qsched : nullptr;  // (null without a schedule: k_linearize then fills Q from the handle's constants)
-  s->st.n_sched = s->n_sched;
+  // (null without a schedule: k_linearize then fills Q from the handle's constants; with one, plain [n_sched][144] from the horizon start on)
+  // (k0 < n_sched while both are set: either setter refuses the other case)
+  s->st.q_sched = s->n_sched > 0 ? s->d_qsched + (size_t)s->k0 * SCHED_WORDS : nullptr;
+  s->st.n_sched = s->n_sched > 0 ? s->n_sched - s->k0 : 0;
   s->total_B = B;
   s->live_hint = 0;  // (nothing known yet: launch_backward takes the batch)
   const CallFacts facts{s->dev.sync_every, d_desired_batch != nullptr, s->st.cost_hist != nullptr, s->early_out != nullptr, 0.0 < s->params.max_iters};

@@ -417,6 +417,22 @@ int qilqr_sharded_set_state_weight_schedule(qilqr_sharded *h, const double *Qs, 
                      [](qilqr_solver *s) { return qilqr_set_state_weight_schedule(s, nullptr, 0); }, checked);
 }
 
+int qilqr_sharded_set_horizon_start(qilqr_sharded *h, int32_t k0) {
+  if (!h || h->solvers.empty()) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  // (checked once, before any shard changes: every shard has the same desired trajectory and schedule.  All or none: a refused start
+  // leaves every shard at the start it had, as the single handle's setter does)
+  const int checked = check_horizon_start(h->solvers[0], k0);
+  if (checked) return checked;
+  std::vector<int> had;
+  for (const qilqr_solver *s : h->solvers) had.push_back(s->k0);
+  return sharded_set(h, 0, [&](qilqr_solver *s, int32_t, int32_t) { return qilqr_set_horizon_start(s, k0); },
+                     [&](qilqr_solver *s) {
+                       for (size_t r = 0; r < h->solvers.size(); ++r)
+                         if (h->solvers[r] == s) s->k0 = had[r];
+                       return QILQR_OK;
+                     });
+}
+
 int qilqr_sharded_set_transport(qilqr_sharded *h, int32_t transport) {
   if (!h) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   if (transport != QILQR_TRANSPORT_AUTO && transport != QILQR_TRANSPORT_RCCL && transport != QILQR_TRANSPORT_PEER_COPY)

@@ -63,6 +63,9 @@ struct qilqr_solver {
   bool sched_symmetric = false;    // ... every Q_i == Q_i^T exactly
   double *d_qsched = nullptr;      // ... the matrices in device memory, [n_sched][144]
   bool own_symmetric = false, own_q_diag = false, own_layout_sym = false, own_layout_ur0 = false;
+  // the horizon start (qilqr_set_horizon_start, horizon.h): knot i of every call reads desired[k0 + i] of the shared desired trajectory and
+  // Qs[k0 + i] of the schedule -- pointer arithmetic in begin_batch, no kernel knows of it
+  int k0 = 0;
   ModelConsts<float> constsf;   // the model constants for the fp32 lane-local kernels
   // workspace
   long cap_B = 0, cap_n = 0;

@@ -1,0 +1,89 @@
+"""Receding-horizon control on device buffers: at every tick the last plan is shifted on the device (QuadrotorILQRBatch.shift_device:
+the flown knots dropped, the horizon's end extended by dynamics steps, knot 0 anchored at the measured state), the handle's horizon
+start advanced along its desired trajectory and schedule (set_horizon_start), and the shifted plan solved again as a warm start
+(solve_batch_device).  Nothing but the measured states goes through the host.
+
+    rh = RecedingHorizon(solver, B, n)
+    first = rh.start(init)                      # a plain solve
+    while flying:
+        res = rh.tick(x0)                       # x0: (B, 13) measured states, words 1..13 of a knot
+        apply(res["u0"])                        # (B, 4) first controls, a view of the plan on the device
+"""
+import numpy as np
+
+from . import capi
+
+
+class RecedingHorizon:
+    """B problems of n knots on `solver` (a QuadrotorILQRBatch whose desired trajectory covers the mission).  Owns two device
+    trajectory buffers, used alternately (the shift does not work in place), and the result arrays of the solves."""
+
+    def __init__(self, solver, B, n):
+        import torch
+        self.solver, self.B, self.n = solver, int(B), int(n)
+        self.device = torch.device("cuda", capi.load().qilqr_device(solver._h))
+        # the solver's own stream as torch sees it: what reads a buffer between the shift and the solve is ordered behind it (_solve)
+        self._stream = torch.cuda.ExternalStream(capi.load().qilqr_stream(solver._h), device=self.device)
+        self._buf = [torch.zeros((self.B, self.n, capi.KNOT), dtype=torch.float64, device=self.device) for _ in range(2)]
+        self._x0 = torch.zeros((self.B, capi.STATE), dtype=torch.float64, device=self.device)
+        self.cost = torch.zeros(self.B, dtype=torch.float64, device=self.device)
+        self.status, self.iters, self.n_bwd, self.n_fwd = (torch.zeros(self.B, dtype=torch.int32, device=self.device) for _ in range(4))
+        self._cur = 0
+        self.k0 = 0        # the horizon start of the last solve
+        self.init = None   # a copy of the initial trajectory of the last solve, when it was asked for (keep_init)
+
+    def _to_device(self, a, dst):
+        import torch
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+        if tuple(a.shape) != tuple(dst.shape):
+            raise TypeError(f"expected shape {tuple(dst.shape)}, not {tuple(a.shape)}")
+        dst.copy_(a)  # (on torch's current stream; the solver's stream is ordered behind it by the calls below)
+        return dst
+
+    def _solve(self, keep_init):
+        import torch
+        buf = self._buf[self._cur]
+        self.init = None
+        if keep_init:
+            # The shift that wrote `buf` was enqueued on the solver's stream and not waited for, and the solver's stream (non-blocking) is
+            # ordered with no other: torch's stream waits for an event recorded behind the shift before the copy reads the buffer.  The
+            # solve below is then ordered behind the copy (solve_batch_device makes the solver's stream wait for torch's).
+            torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
+            self.init = buf.clone()
+        self.solver.solve_batch_device(buf, buf, self.cost, self.status, self.iters, self.n_bwd, self.n_fwd)  # (in place: drained on return)
+        return dict(u0=buf[:, 0, 14:18], traj=buf, cost=self.cost, status=self.status, iters=self.iters)
+
+    def start(self, init, keep_init=False):
+        """A plain solve of `init` (B, n, 18; NumPy or torch) from the start of the handle's desired trajectory (horizon start 0)."""
+        self.solver.set_horizon_start(0)
+        self.k0 = 0
+        self._to_device(init, self._buf[self._cur])
+        return self._solve(keep_init)
+
+    def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False):
+        """One control tick: the horizon start advanced by `steps` (advance=False: the desired trajectory is relative to the vehicle and
+        stays), the last plan shifted into the other buffer with knot 0 at x0 (B, 13; NumPy or torch; None keeps the plan's own), and the
+        solve from there.  Returns views (valid until the next tick but one) of the first controls u0 = traj[:, 0, 14:18], the plan, cost,
+        status and iterations, read after the solve has drained the solver's stream.  keep_init=True also keeps a copy of the shifted plan
+        the solve started from in `self.init`: made on torch's current stream, which is made to wait for the shift on the solver's stream
+        first (the two streams are ordered with each other only where one is told to wait).  A tick that is refused -- steps or tail out of
+        range, or no window of n knots left behind the new start -- raises and leaves the object and the handle's start as they were."""
+        steps = int(steps)
+        x0 = None if x0 is None else self._to_device(x0, self._x0)
+        # (refuses steps or a tail out of range before anything of this object or of the handle has changed; the buffer it writes holds the
+        # plan before last, which nobody reads any more)
+        self.solver.shift_device(self._buf[self._cur], self._buf[self._cur ^ 1], x0=x0, steps=steps, tail=tail)
+        had_k0, had_cur = self.k0, self._cur
+        try:
+            if advance:
+                self.solver.set_horizon_start(had_k0 + steps)
+                self.k0 = had_k0 + steps
+            self._cur ^= 1
+            return self._solve(keep_init)
+        except Exception:
+            # a refused start or solve (past the end of the mission no window of n knots is left) leaves the last plan, its buffer and the
+            # start it was solved at in force
+            self.solver.set_horizon_start(had_k0)
+            self.k0, self._cur = had_k0, had_cur
+            raise

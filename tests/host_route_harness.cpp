@@ -80,6 +80,38 @@ extern "C" int hr_route(const long *in, long *out) {
   return (int)(o - out);
 }
 
+// The k_linearize key and the backward kernel of a stand-alone pass or a batch solve of B problems, from the RouteInputs a handle makes of
+// itself (tests/linearize_cases.py restates host/api_handle.h), `scheduled` and `problem_obstacles` among them.
+// in:  {symmetric, q_diag, layout_kind, f32, integrator, limited, modeled, obstacles, problem_obstacles, scheduled, force_general, B}
+// out: {lin_kind, integrator, tiled, f32, ext, backward kind (route.h, BackwardKind), admitted by lin_instantiated}
+extern "C" int hr_lin_route(const long *in, long *out) {
+  RouteInputs ri;
+  ri.symmetric = in[0];
+  ri.q_diag = in[1];
+  ri.layout_kind = (int)in[2];
+  ri.f32 = in[3];
+  ri.integrator = (int)in[4];
+  ri.limited = in[5];
+  ri.modeled = in[6];
+  ri.obstacles = in[7];
+  ri.problem_obstacles = in[8];
+  ri.scheduled = in[9];
+  ri.dev.force_general = (int)in[10];
+  ri.dev.sync_every = 2;
+  const Route r = plan_route(ri, in[11], CallFacts{});
+  const ExtArgs &x = r.linearize_ext;
+  const int ext = (x.models ? LIN_MODELS : LIN_PLAIN) | (x.obstacles ? LIN_OBSTACLES : LIN_PLAIN) | (x.problem_obstacles ? LIN_PROBLEM : LIN_PLAIN);
+  long *o = out;
+  *o++ = r.lin_kind;
+  *o++ = r.integrator;
+  *o++ = r.tiled;
+  *o++ = r.f32;
+  *o++ = ext;
+  *o++ = r.backward;
+  *o++ = lin_instantiated(lin_key(r.lin_kind, r.integrator, r.tiled, r.f32, ext));
+  return (int)(o - out);
+}
+
 // Every key of the key space that lin_instantiated admits, as rows of {lin_kind, integrator, tiled, f32, ext} in key order; returns the
 // number of rows (cap rows are written), or -1 when the rule by key and the rule by fields disagree or a key leaves the key space.
 extern "C" int hr_lin_keys(long *out, int cap) {

@@ -421,6 +421,48 @@ int qilqr_shift_batch_device(qilqr_solver *s, const double *d_traj, const double
 int qilqr_shift_batch(qilqr_solver *s, const double *traj, const double *x0, int32_t B, int32_t n, int32_t steps, int32_t tail,
                       double *out);
 
+/* ---- the other half of the plan: its feedback law (an extension; the reference keeps its gains inside ILQR::solve).  iLQR computes, with
+ * every plan, the time-varying law u = u_i + K_i (x (-) x_i) that flies it from a state off the plan.  Two calls bring it to a caller of
+ * the device path: the gains about a plan that sits in device memory, and the law applied from measured or sampled states.
+ *
+ * qilqr_backwards_pass_device is qilqr_backwards_pass over plain device arrays (d_traj B x n x 18, d_gains B x n x 52, d_terms B x 2 or
+ * NULL): the same linearisation and backward pass, honouring every extension the host form honours (schedule, spheres, limits, models,
+ * integrator, horizon start), the same bits, without the two copies of B x n x 52 doubles over the host.  It is a pass of its own, and not
+ * a by-product of the solve, because the gains a solve holds when it returns belong to the iterate BEFORE its last accepted step: they
+ * were computed about the trajectory the last line search started from.  Gains about the RETURNED plan are one more backward pass on it --
+ * this one.  It returns after the handle's stream has drained, as qilqr_solve_batch_device does (order the inputs the same way).
+ *
+ * The closed loop.  plan is B x n x 18, gains B x n x 52 (of which the feed-forward part k, words 0..3 of a knot, is NOT read: the law at
+ * alpha = 0), x0 is B x S x QILQR_STATE: S states per plan.  0 <= i0 <= i1 <= n - 1, S >= 1.  Sample (b, j) has state x0[b, j] at knot
+ * i0, and for i = i0 .. i1:
+ *   dx = x (-) plan[b, i]                      the 12 tangent words the solver's rollout forms
+ *   u  = plan[b, i, 14:18] + K_i dx            clamped to the thrust limits while they are set
+ *   knot i of the sample is recorded           its time is plan[b, i, 0], then the state, then u
+ *   if i < i1: one dynamics step under u       the handle's: its dt, its integrator, and models[b S + j] while per-problem models are set --
+ *                                              they must then have been set for B S problems; plant / model mismatch is expressed this way
+ * in the arithmetic of the solver's own rollout: with S = 1, x0 = plan[:, 0, 1:14], i0 = 0 and i1 = n - 1 the result has the bits of
+ * qilqr_forward_sim(plan, gains, alpha = 0) on a handle with single_wave_rollout = 1.  A sample's bits depend on its own inputs only --
+ * not on S, on j, or on which of the kernel's two forms carried it (a wavefront of 64 samples of one plan that shares the plan's operands,
+ * or a lane per sample for small S).  i0 = i1 is the plain policy evaluation at a measured state.  No cost is evaluated: spheres, schedules
+ * and the horizon start play no part.
+ *   d_out_traj    B x S x n x 18 or NULL: knots i0 .. i1 of every sample are written, every other knot is left untouched; with NULL no
+ *                 trajectory store is issued (a Monte-Carlo caller reads the statistics only)
+ *   d_out_stats   B x S x QILQR_CL_STATS or NULL, from the dx the law computes anyway: {max_i |dx_i[0:3]|, max_i |dx_i[3:6]|, |dx_i1|,
+ *                 the number of (knot, rotor) pairs that were clamped, as a double} -- Euclidean norms of the position error, the
+ *                 rotation error and, at the last knot, of all 12 words
+ * Both forms: QILQR_ERR_INVALID_ARG, before the device is touched, for a NULL plan, gains or x0, both outputs NULL, a non-positive B, n or
+ * S, knots out of range, an array that is not 16-byte aligned, an output that overlaps an input or the other output, a NULL or
+ * mixed-precision handle, and per-problem models set for another count than B S.  qilqr_closed_loop (host arrays) checks x0's quaternions
+ * (QILQR_ERR_BAD_QUATERNION, naming problem and sample) and returns when the outputs are written.  The device form checks nothing on the
+ * device, ENQUEUES on the handle's stream and returns WITHOUT draining it, with the ordering rules of the device form of the shift.
+ * Sharded handles have neither call: use a shard's solver (qilqr_sharded_solver) with the arrays of its device. */
+#define QILQR_CL_STATS 4
+int qilqr_backwards_pass_device(qilqr_solver *s, const double *d_traj, int32_t B, int32_t n, double *d_gains, double *d_terms);
+int qilqr_closed_loop_device(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0, int32_t B, int32_t n,
+                             int32_t S, int32_t i0, int32_t i1, double *d_out_traj, double *d_out_stats);
+int qilqr_closed_loop(qilqr_solver *s, const double *plan, const double *gains, const double *x0, int32_t B, int32_t n, int32_t S,
+                      int32_t i0, int32_t i1, double *out_traj, double *out_stats);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -556,8 +598,8 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * `compaction`).  qilqr_set_control_limits, QILQR_STATUS_QP_FAILED, qilqr_set_batch_models, qilqr_sharded_set_batch_models,
  * qilqr_set_obstacles, qilqr_sharded_set_obstacles, QILQR_MAX_OBSTACLES, qilqr_set_batch_obstacles, qilqr_sharded_set_batch_obstacles,
  * QILQR_OBSTACLE_WORDS, qilqr_set_state_weight_schedule, qilqr_sharded_set_state_weight_schedule, qilqr_set_horizon_start,
- * qilqr_sharded_set_horizon_start, qilqr_shift_batch, qilqr_shift_batch_device, QILQR_STATE, QILQR_TAIL_HOLD and QILQR_TAIL_HOVER were added
- * within version 7: no structure changed. */
+ * qilqr_sharded_set_horizon_start, qilqr_shift_batch, qilqr_shift_batch_device, QILQR_STATE, QILQR_TAIL_HOLD, QILQR_TAIL_HOVER,
+ * qilqr_backwards_pass_device, qilqr_closed_loop, qilqr_closed_loop_device and QILQR_CL_STATS were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

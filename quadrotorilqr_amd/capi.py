@@ -36,6 +36,7 @@ MAX_OBSTACLES = 64  # QILQR_MAX_OBSTACLES: spheres per handle (set_obstacles), a
 OBSTACLE_WORDS = 8  # QILQR_OBSTACLE_WORDS: {cx, cy, cz, vx, vy, vz, radius, weight} of a per-problem sphere (set_batch_obstacles)
 STATE = 13  # QILQR_STATE: words 1..13 of a knot, t(3), q w,x,y,z, v_lin(3), v_ang(3) (shift's x0)
 TAILS = {"hold": 0, "hover": 1}  # QILQR_TAIL_HOLD, QILQR_TAIL_HOVER: the control of the knots a shift appends
+CL_STATS = 4  # QILQR_CL_STATS: max position error, max rotation error, |dx| at the last knot, clamped (knot, rotor) pairs (closed_loop)
 
 # every symbol include/quadrotor_ilqr.h declares
 EXPORTS = (
@@ -46,6 +47,7 @@ EXPORTS = (
     "qilqr_set_obstacles", "qilqr_sharded_set_obstacles", "qilqr_set_batch_obstacles", "qilqr_sharded_set_batch_obstacles",
     "qilqr_set_state_weight_schedule", "qilqr_sharded_set_state_weight_schedule",
     "qilqr_set_horizon_start", "qilqr_sharded_set_horizon_start", "qilqr_shift_batch", "qilqr_shift_batch_device",
+    "qilqr_backwards_pass_device", "qilqr_closed_loop", "qilqr_closed_loop_device",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -119,6 +121,9 @@ def load():
             f.argtypes = [C.c_void_p, C.c_int32]
         for f in (lib.qilqr_shift_batch, lib.qilqr_shift_batch_device):
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        lib.qilqr_backwards_pass_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        for f in (lib.qilqr_closed_loop, lib.qilqr_closed_loop_device):
+            f.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 2
         _lib = lib
     return _lib
 
@@ -625,6 +630,99 @@ class QuadrotorILQRBatch:
                 _raise(rc)
         vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
         rc = load().qilqr_shift_batch_device(self._h, vp(traj), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(int(steps)), C.c_int32(tail), vp(out))
+        if rc:
+            _raise(rc)
+
+    # ---- the plan's feedback law: gains about a plan on the device, and the law flown from given states
+    def _device_tensors(self, specs):
+        """checks of the device entry points: (tensor, name, shape) float64, contiguous, on the solver's device; None is skipped"""
+        import torch
+        dev_index = load().qilqr_device(self._h)
+        for t, name, shape in specs:
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != dev_index:
+                raise TypeError(f"{name} must be a CUDA tensor on device {dev_index}")
+            if t.dtype != torch.float64:
+                raise TypeError(f"{name} must be {torch.float64}")
+            if tuple(t.shape) != shape:
+                raise TypeError(f"{name} must have shape {shape}, not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise TypeError(f"{name} must be contiguous")
+
+    def _wait_current_stream(self, t):
+        import torch
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(t.device))
+        rc = load().qilqr_stream_wait_event(self._h, C.c_void_p(ev.cuda_event))
+        if rc:
+            _raise(rc)
+
+    def backwards_pass_device(self, traj, gains, terms=None, wait_current_stream=True):
+        """qilqr_backwards_pass_device on torch tensors: traj float64 (B, n, 18) -> gains (B, n, 52) and, when given, terms (B, 2), the bits
+        of backwards_pass(traj) without the trip over the host.  Ordered behind torch's current stream (wait_current_stream) and
+        finished when this returns, as solve_batch_device."""
+        if traj is None or traj.dim() != 3 or traj.shape[2] != KNOT:
+            raise TypeError("traj must be (B, n, 18)")
+        if gains is None:
+            raise TypeError("gains must be a (B, n, 52) tensor")
+        B, n = int(traj.shape[0]), int(traj.shape[1])
+        self._device_tensors(((traj, "traj", (B, n, KNOT)), (gains, "gains", (B, n, GAIN)), (terms, "terms", (B, 2))))
+        if wait_current_stream:
+            self._wait_current_stream(traj)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        rc = load().qilqr_backwards_pass_device(self._h, vp(traj), C.c_int32(B), C.c_int32(n), vp(gains), vp(terms))
+        if rc:
+            _raise(rc)
+
+    def closed_loop(self, plan, gains, x0, i0=0, i1=None, traj=True, stats=True):
+        """qilqr_closed_loop, host arrays: the law u = u_i + K_i (x (-) plan_i) of plan (B, n, 18) and gains (B, n, 52) flown from the
+        states x0 (B, S, 13) -- or (B, 13): S = 1 -- over knots i0 .. i1 (i1 = None: n - 1) with the handle's step, thrust limits and
+        per-problem models (B * S of them: model b S + j flies sample (b, j)).  Returns a dict: traj (B, S, n, 18), NaN outside knots
+        i0 .. i1 (traj=True), and stats (B, S, 4): max position error, max rotation error, |dx| at knot i1, clamped (knot, rotor) pairs
+        (stats=True)."""
+        plan, gains, x0 = _d16(plan), _d16(gains), _d16(x0)
+        if plan.ndim != 3 or plan.shape[2] != KNOT:
+            raise TypeError("plan must be (B, n, 18)")
+        B, n = plan.shape[0], plan.shape[1]
+        if gains.shape != (B, n, GAIN):
+            raise TypeError(f"gains must be ({B}, {n}, {GAIN})")
+        if x0.ndim == 2:
+            x0 = x0.reshape(x0.shape[0], 1, x0.shape[1])
+        if x0.ndim != 3 or x0.shape[0] != B or x0.shape[2] != STATE:
+            raise TypeError(f"x0 must be ({B}, S, {STATE}): words 1..13 of a knot per sample")
+        S = x0.shape[1]
+        i1 = n - 1 if i1 is None else int(i1)
+        out_traj = _d16(np.full((B, S, n, KNOT), np.nan)) if traj else None
+        out_stats = _d16(np.zeros((B, S, CL_STATS))) if stats else None
+        vp = lambda a: C.c_void_p(0 if a is None else a.ctypes.data)
+        rc = load().qilqr_closed_loop(self._h, vp(plan), vp(gains), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1),
+                                      vp(out_traj), vp(out_stats))
+        if rc:
+            _raise(rc)
+        return {k: v for k, v in (("traj", out_traj), ("stats", out_stats)) if v is not None}
+
+    def closed_loop_device(self, plan, gains, x0, out_traj=None, out_stats=None, i0=0, i1=None, wait_current_stream=True):
+        """qilqr_closed_loop_device on torch tensors, checked like shift_device: plan (B, n, 18), gains (B, n, 52), x0 (B, S, 13), out_traj
+        (B, S, n, 18) or None, out_stats (B, S, 4) or None, float64, contiguous, on the solver's device.  Only knots i0 .. i1 of out_traj
+        are written.  ENQUEUED on the solver's own stream -- behind whatever torch has enqueued on its current stream
+        (wait_current_stream) -- and not waited for: stream ordering as for shift_device."""
+        if plan is None or plan.dim() != 3 or plan.shape[2] != KNOT:
+            raise TypeError("plan must be (B, n, 18)")
+        B, n = int(plan.shape[0]), int(plan.shape[1])
+        if x0 is None or x0.dim() != 3:
+            raise TypeError(f"x0 must be ({B}, S, {STATE})")
+        S = int(x0.shape[1])
+        i1 = n - 1 if i1 is None else int(i1)
+        self._device_tensors(((plan, "plan", (B, n, KNOT)), (gains, "gains", (B, n, GAIN)), (x0, "x0", (B, S, STATE)),
+                              (out_traj, "out_traj", (B, S, n, KNOT)), (out_stats, "out_stats", (B, S, CL_STATS))))
+        if gains is None:
+            raise TypeError("gains must be a (B, n, 52) tensor")
+        if wait_current_stream:
+            self._wait_current_stream(plan)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        rc = load().qilqr_closed_loop_device(self._h, vp(plan), vp(gains), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)),
+                                             C.c_int32(i1), vp(out_traj), vp(out_stats))
         if rc:
             _raise(rc)
 

@@ -1,5 +1,6 @@
 // host/api_calls.h -- the C ABI of the computing calls on one handle: the batch solves, qilqr_solve, the four stand-alone passes, the
-// pinned host memory for their callers, and the receding-horizon shift (whose kernel is shift.hip's).  Part of ilqr_capi.hip's translation unit.
+// pinned host memory for their callers, the receding-horizon shift (whose kernel is shift.hip's), the backward pass over device arrays and the
+// closed-loop flights of a plan (whose kernel is closed_loop.hip's).  Part of ilqr_capi.hip's translation unit.
 #pragma once
 
 extern "C" {
@@ -361,6 +362,96 @@ int qilqr_shift_batch(qilqr_solver *s, const double *traj, const double *x0, int
   if (e == hipSuccess) e = drained;
   if (e == hipSuccess) e = hipGetLastError();
   if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("qilqr_shift_batch: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+
+// ---- gains about a plan that already sits on the device: qilqr_backwards_pass over plain device arrays -- the same linearise / k_init /
+// launch_backward sequence through to_tiled / from_tiled, without the io scratch and the two copies over PCIe
+int qilqr_backwards_pass_device(qilqr_solver *s, const double *d_traj, int32_t B, int32_t n, double *d_gains, double *d_terms) {
+  if (!s || !d_traj || !d_gains) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  int rc = begin_batch(s, B, n, nullptr, E_PASS);
+  if (rc) return rc;
+  if ((rc = to_tiled(s, d_traj, s->st.traj[0], B, n, 18))) return rc;
+  if ((rc = launch_linearize(s, B, n, 0, 0))) return rc;
+  launch(s, K_OTHER, k_init, dim3(cdiv(B, 64)), dim3(64), s->params, s->st, (int)B, (int)n);
+  if ((rc = launch_backward(s, B, n, 1))) return rc;
+  if ((rc = from_tiled(s, d_gains, s->st.gains, s->st.gains, nullptr, 0, B, n, 52))) return rc;
+  if (d_terms) HIP_TRY(hipMemcpyAsync(d_terms, s->st.terms, sizeof(double) * 2 * B, hipMemcpyDeviceToDevice, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipGetLastError());
+  return device_error(s);
+}
+
+// ---- the plan's feedback law flown from given states: k_closed_loop (closed_loop_kernels.h, compiled by closed_loop.hip) on the caller's arrays
+namespace {
+// what both forms refuse (closed_loop_launch.h: the rule, from facts alone; the pointers are the caller's, host or device ones)
+int closed_loop_refuse(const qilqr_solver *s, const double *plan, const double *gains, const double *x0, int32_t B, int32_t n, int32_t S,
+                       int32_t i0, int32_t i1, const double *out_traj, const double *out_stats) {
+  const ClosedLoopCall call{plan, gains, x0, out_traj, out_stats, B, n, S, i0, i1, s != nullptr, s && s->f32, s && s->modeled, s ? s->models_B : 0};
+  const char *why = closed_loop_refusal(call);
+  if (!why) return QILQR_OK;
+  std::string text = why;
+  if (s && s->modeled && !s->f32 && s->models_B != (long)B * S)
+    text += ": they were set for " + std::to_string(s->models_B) + ", this call has B * S = " + std::to_string((long)B * S);
+  return fail(QILQR_ERR_INVALID_ARG, text);
+}
+int closed_loop_enqueue(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0, int32_t B, int32_t n, int32_t S,
+                        int32_t i0, int32_t i1, double *d_out_traj, double *d_out_stats) {
+  const ClosedLoopLaunch call{d_plan, d_gains, d_x0, d_out_traj, d_out_stats, B, n, S, i0, i1, s->integrator, s->limited ? &s->limits : nullptr,
+                              s->modeled ? s->d_models : nullptr};
+  const hipError_t e = launch_closed_loop(s->stream, s->consts, call);
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_closed_loop: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+}  // namespace
+
+static_assert(QILQR_CL_STATS == 4, "closed_loop_kernels.h and the C header agree on the words of a sample's statistics");
+int qilqr_closed_loop_device(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0, int32_t B, int32_t n, int32_t S,
+                             int32_t i0, int32_t i1, double *d_out_traj, double *d_out_stats) {
+  int rc = closed_loop_refuse(s, d_plan, d_gains, d_x0, B, n, S, i0, i1, d_out_traj, d_out_stats);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return closed_loop_enqueue(s, d_plan, d_gains, d_x0, B, n, S, i0, i1, d_out_traj, d_out_stats);  // (enqueued on the handle's stream; not waited for)
+}
+
+int qilqr_closed_loop(qilqr_solver *s, const double *plan, const double *gains, const double *x0, int32_t B, int32_t n, int32_t S, int32_t i0,
+                      int32_t i1, double *out_traj, double *out_stats) {
+  int rc = closed_loop_refuse(s, plan, gains, x0, B, n, S, i0, i1, out_traj, out_stats);
+  if (rc) return rc;
+  for (long r = 0; r < (long)B * S; ++r) {  // as the initial trajectories are checked (manif's constructor check), naming the sample
+    const double *q = x0 + r * QILQR_STATE + 3;
+    const double nn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (!(std::fabs(nn - 1.0) <= 1e-10))
+      return fail(QILQR_ERR_BAD_QUATERNION, "x0: quaternion not normalized at problem " + std::to_string(r / S) + ", sample " + std::to_string(r % S));
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  struct Scratch {  // freed on every return path
+    double *p = nullptr;
+    ~Scratch() {
+      if (p) (void)hipFree(p);
+    }
+  } scratch;
+  // (every count but x0's is even, and x0 goes last: each array starts on 16 bytes)
+  const size_t samples = (size_t)B * S, pc = 18 * (size_t)B * n, gc = 52 * (size_t)B * n, xc = (size_t)QILQR_STATE * samples;
+  const size_t tc = out_traj ? 18 * samples * n : 0, sc = out_stats ? QILQR_CL_STATS * samples : 0;
+  HIP_TRY(hipMalloc((void **)&scratch.p, sizeof(double) * (pc + gc + tc + sc + xc)));
+  double *d_plan = scratch.p, *d_gains = d_plan + pc, *d_traj = d_gains + gc, *d_stats = d_traj + tc, *d_x0 = d_stats + sc;
+  HIP_TRY(hipMemcpyAsync(d_plan, plan, sizeof(double) * pc, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d_gains, gains, sizeof(double) * gc, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d_x0, x0, sizeof(double) * xc, hipMemcpyHostToDevice, s->stream));
+  hipError_t e = hipSuccess;
+  if ((rc = closed_loop_enqueue(s, d_plan, d_gains, d_x0, B, n, S, i0, i1, out_traj ? d_traj : nullptr, out_stats ? d_stats : nullptr)) == QILQR_OK) {
+    // knots i0 .. i1 of every sample, and nothing else of the caller's array: rows of (i1 - i0 + 1) knots at a pitch of n knots
+    const size_t pitch = sizeof(double) * 18 * (size_t)n, off = 18 * (size_t)i0;
+    if (out_traj)
+      e = hipMemcpy2DAsync(out_traj + off, pitch, d_traj + off, pitch, sizeof(double) * 18 * (size_t)(i1 - i0 + 1), samples, hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess && out_stats) e = hipMemcpyAsync(out_stats, d_stats, sizeof(double) * sc, hipMemcpyDeviceToHost, s->stream);
+  }
+  const hipError_t drained = hipStreamSynchronize(s->stream);  // (the copies read and write the caller's arrays, the kernel the scratch: finished before either goes)
+  if (rc) return rc;
+  if (e == hipSuccess) e = drained;
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("qilqr_closed_loop: ") + hipGetErrorString(e));
   return QILQR_OK;
 }
 }  // extern "C"

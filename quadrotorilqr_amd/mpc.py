@@ -8,6 +8,10 @@ start advanced along its desired trajectory and schedule (set_horizon_start), an
     while flying:
         res = rh.tick(x0)                       # x0: (B, 13) measured states, words 1..13 of a knot
         apply(res["u0"])                        # (B, 4) first controls, a view of the plan on the device
+
+Between two ticks the plan can be flown closed loop: tick(x0, gains=True) also leaves the feedback gains about the new plan on the device
+(QuadrotorILQRBatch.backwards_pass_device), and control(x, i) evaluates the law u = u_i + K_i (x (-) plan_i) at measured states
+(closed_loop_device with one sample per plan and i0 = i1 = i).
 """
 import numpy as np
 
@@ -31,6 +35,10 @@ class RecedingHorizon:
         self._cur = 0
         self.k0 = 0        # the horizon start of the last solve
         self.init = None   # a copy of the initial trajectory of the last solve, when it was asked for (keep_init)
+        # the feedback law of the last plan: allocated by the first start / tick that asks for gains, and by the first control()
+        self.gains = self.terms = None   # (B, n, 52), (B, 2): about the plan of the last solve while _have_gains
+        self._have_gains = False
+        self._xc = self._ctl = None      # control()'s states (B, 1, 13) and the knots it writes (B, 1, n, 18)
 
     def _to_device(self, a, dst):
         import torch
@@ -41,7 +49,7 @@ class RecedingHorizon:
         dst.copy_(a)  # (on torch's current stream; the solver's stream is ordered behind it by the calls below)
         return dst
 
-    def _solve(self, keep_init):
+    def _solve(self, keep_init, gains=False):
         import torch
         buf = self._buf[self._cur]
         self.init = None
@@ -52,22 +60,53 @@ class RecedingHorizon:
             torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
             self.init = buf.clone()
         self.solver.solve_batch_device(buf, buf, self.cost, self.status, self.iters, self.n_bwd, self.n_fwd)  # (in place: drained on return)
-        return dict(u0=buf[:, 0, 14:18], traj=buf, cost=self.cost, status=self.status, iters=self.iters)
+        res = dict(u0=buf[:, 0, 14:18], traj=buf, cost=self.cost, status=self.status, iters=self.iters)
+        self._have_gains = False
+        if gains:
+            # The gains a solve ends with belong to the iterate before its last accepted step: the law about the plan it returned is one
+            # more backward pass on that plan (at the handle's current horizon start: the one the plan was solved at).
+            if self.gains is None:
+                self.gains = torch.zeros((self.B, self.n, capi.GAIN), dtype=torch.float64, device=self.device)
+                self.terms = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)
+            self.solver.backwards_pass_device(buf, self.gains, self.terms)  # (drained on return)
+            self._have_gains = True
+            res["gains"] = self.gains
+        return res
 
-    def start(self, init, keep_init=False):
-        """A plain solve of `init` (B, n, 18; NumPy or torch) from the start of the handle's desired trajectory (horizon start 0)."""
+    def start(self, init, keep_init=False, gains=False):
+        """A plain solve of `init` (B, n, 18; NumPy or torch) from the start of the handle's desired trajectory (horizon start 0).
+        gains=True: as for tick."""
         self.solver.set_horizon_start(0)
         self.k0 = 0
         self._to_device(init, self._buf[self._cur])
-        return self._solve(keep_init)
+        return self._solve(keep_init, gains)
 
-    def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False):
+    def control(self, x, i=0):
+        """The (B, 4) controls of the last plan's feedback law at knot `i` for the measured states x (B, 13; NumPy or torch):
+        u = plan[:, i, 14:18] + K_i (x (-) plan[:, i]), clamped to the handle's thrust limits while they are set.  Needs the gains of the
+        last plan (start / tick with gains=True).  A new tensor, complete on torch's current stream."""
+        import torch
+        if not self._have_gains:
+            raise RuntimeError("control() needs the gains of the last plan: call start() or tick() with gains=True")
+        if self._xc is None:
+            self._xc = torch.zeros((self.B, 1, capi.STATE), dtype=torch.float64, device=self.device)
+            self._ctl = torch.zeros((self.B, 1, self.n, capi.KNOT), dtype=torch.float64, device=self.device)
+        self._to_device(x, self._xc[:, 0])
+        i = int(i)
+        self.solver.closed_loop_device(self._buf[self._cur], self.gains, self._xc, out_traj=self._ctl, i0=i, i1=i)
+        # (enqueued on the solver's stream and not waited for: torch's stream waits for it before it reads the knot)
+        torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
+        return self._ctl[:, 0, i, 14:18].clone()
+
+    def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False, gains=False):
         """One control tick: the horizon start advanced by `steps` (advance=False: the desired trajectory is relative to the vehicle and
         stays), the last plan shifted into the other buffer with knot 0 at x0 (B, 13; NumPy or torch; None keeps the plan's own), and the
         solve from there.  Returns views (valid until the next tick but one) of the first controls u0 = traj[:, 0, 14:18], the plan, cost,
         status and iterations, read after the solve has drained the solver's stream.  keep_init=True also keeps a copy of the shifted plan
         the solve started from in `self.init`: made on torch's current stream, which is made to wait for the shift on the solver's stream
-        first (the two streams are ordered with each other only where one is told to wait).  A tick that is refused -- steps or tail out of
+        first (the two streams are ordered with each other only where one is told to wait).  gains=True also leaves the feedback gains about
+        the new plan in `self.gains` (B, n, 52; a device buffer this object owns, allocated at the first such call) and returns them under
+        "gains": one more backward pass on the plan (backwards_pass_device), what control() evaluates.  A tick that is refused -- steps or tail out of
         range, or no window of n knots left behind the new start -- raises and leaves the object and the handle's start as they were."""
         steps = int(steps)
         x0 = None if x0 is None else self._to_device(x0, self._x0)
@@ -80,7 +119,7 @@ class RecedingHorizon:
                 self.solver.set_horizon_start(had_k0 + steps)
                 self.k0 = had_k0 + steps
             self._cur ^= 1
-            return self._solve(keep_init)
+            return self._solve(keep_init, gains)
         except Exception:
             # a refused start or solve (past the end of the mission no window of n knots is left) leaves the last plan, its buffer and the
             # start it was solved at in force

@@ -444,7 +444,7 @@ int qilqr_shift_batch(qilqr_solver *s, const double *traj, const double *x0, int
  * qilqr_forward_sim(plan, gains, alpha = 0) on a handle with single_wave_rollout = 1.  A sample's bits depend on its own inputs only --
  * not on S, on j, or on which of the kernel's two forms carried it (a wavefront of 64 samples of one plan that shares the plan's operands,
  * or a lane per sample for small S).  i0 = i1 is the plain policy evaluation at a measured state.  No cost is evaluated: spheres, schedules
- * and the horizon start play no part.
+ * and the horizon start play no part (qilqr_closed_loop_scored, below, scores the flight).
  *   d_out_traj    B x S x n x 18 or NULL: knots i0 .. i1 of every sample are written, every other knot is left untouched; with NULL no
  *                 trajectory store is issued (a Monte-Carlo caller reads the statistics only)
  *   d_out_stats   B x S x QILQR_CL_STATS or NULL, from the dx the law computes anyway: {max_i |dx_i[0:3]|, max_i |dx_i[3:6]|, |dx_i1|,
@@ -462,6 +462,51 @@ int qilqr_closed_loop_device(qilqr_solver *s, const double *d_plan, const double
                              int32_t S, int32_t i0, int32_t i1, double *d_out_traj, double *d_out_stats);
 int qilqr_closed_loop(qilqr_solver *s, const double *plan, const double *gains, const double *x0, int32_t B, int32_t n, int32_t S,
                       int32_t i0, int32_t i1, double *out_traj, double *out_stats);
+
+/* The scored flight (extension): the closed loop above flown under a disturbance and scored on the device -- what a Monte-Carlo caller
+ * flies samples for, without the B x S x n x 18 trajectories.  The law, the clamp, the step, out_traj and out_stats are
+ * qilqr_closed_loop's, word for word; with wrench, desired and out_score all NULL the call launches the same kernels and gives the bits
+ * of qilqr_closed_loop[_device].
+ *
+ * The disturbance.  wrench is NULL or B x S x n_w x QILQR_WRENCH doubles {F_x, F_y, F_z, tau_x, tau_y, tau_z}: F a force in newtons in
+ * the WORLD frame, tau a torque in N m in the BODY frame.  n_w = 1: one wrench per sample for the whole flight; n_w = n: wrench[b, j, i]
+ * acts during the step from knot i to knot i + 1 (a zero-order hold); rows of steps outside i0 .. i1 - 1 are never read.  The wrench
+ * enters the continuous dynamics where thrust and moment do, with the sample's model.  With R = R(q) the attitude of the state the
+ * acceleration is evaluated at (under Runge-Kutta each stage's own, the wrench held over the four stages), in this order:
+ *     f[k]       = R[0][k] F_x + R[1][k] F_y + R[2][k] F_z        (R^T F: the velocities of this model are body-frame)
+ *     acc_lin[k] = a[k] + f[k] / mass                             (a[k]: the undisturbed linear acceleration, formed first)
+ *     rhs[k]     = (M[k] - (w x I w)[k]) + tau[k]                 (then acc_ang = I^-1 rhs, as without a wrench)
+ * one text for both forms of the kernel, so a sample's bits still depend on its own inputs only.  A zero wrench flies the flight
+ * without one (equal values).
+ *
+ * The score.  out_score is NULL or B x S x QILQR_CL_SCORE doubles {cost, min_clearance, knot_of_min_clearance, knots_in_collision}:
+ *   cost            the sum over i = i0 .. i1, in knot order, of the handle's knot cost at the flown state and the applied (clamped)
+ *                   control: the tracking cost with the handle's Q (Qs[k0 + i] while a schedule is set) and R against desired[k0 + i] of
+ *                   the handle -- or, when d_desired (B x n x 18, one per plan, as desired_batch of the solves) is given, against
+ *                   d_desired[b, i], whatever k0 is -- then the shared spheres, then row b of the per-problem table (centres at
+ *                   c + i dt v), each table in index order: what qilqr_cost_trajectory charges those knots of that trajectory
+ *   min_clearance   the minimum of |p - c_j(i)| - radius_j over i = i0 .. i1 and every sphere of both tables; +inf without spheres
+ *   knot_of_min_clearance   the knot where it is attained, the first on ties; -1 without spheres
+ *   knots_in_collision      the number of knots whose smallest clearance is < 0
+ * At a knot: h_j = radius_j - |p - c_j|; if h_j > 0 the knot cost grows by (weight_j h_j) h_j; the clearance is -h_j.  A sphere of
+ * weight 0 leaves the cost's bits and still counts for the clearance (an "observe only" obstacle; inflate its radius by the vehicle's).
+ * A NaN is taken, not dropped, as the maxima of the statistics take one.
+ *
+ * Any of the three outputs may be NULL, not all three; with out_traj NULL no trajectory store is issued.  Refused, after what
+ * qilqr_closed_loop refuses about the same arguments: n_w other than 1 or n while a wrench is given; wrench, desired or out_score off a
+ * 16-byte boundary; the score array overlapping an input or another output (or an output the wrench or desired); then, after the
+ * handle's own refusals, scoring while a per-problem sphere table is set for another B (QILQR_ERR_INVALID_ARG all), and
+ * QILQR_ERR_LENGTH_MISMATCH when scoring without desired needs i1 >= n_desired - k0, or with a schedule i1 >= n_knots - k0.  The host
+ * form also refuses a non-finite wrench word, naming (problem, sample, knot).  The device form checks nothing on the device, ENQUEUES
+ * on the handle's stream and does not drain it, with the ordering rules of qilqr_closed_loop_device. */
+#define QILQR_WRENCH 6
+#define QILQR_CL_SCORE 4
+int qilqr_closed_loop_scored_device(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0,
+                                    const double *d_wrench, int32_t n_w, const double *d_desired, int32_t B, int32_t n, int32_t S,
+                                    int32_t i0, int32_t i1, double *d_out_traj, double *d_out_stats, double *d_out_score);
+int qilqr_closed_loop_scored(qilqr_solver *s, const double *plan, const double *gains, const double *x0, const double *wrench,
+                             int32_t n_w, const double *desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1,
+                             double *out_traj, double *out_stats, double *out_score);
 
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
@@ -599,7 +644,8 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * qilqr_set_obstacles, qilqr_sharded_set_obstacles, QILQR_MAX_OBSTACLES, qilqr_set_batch_obstacles, qilqr_sharded_set_batch_obstacles,
  * QILQR_OBSTACLE_WORDS, qilqr_set_state_weight_schedule, qilqr_sharded_set_state_weight_schedule, qilqr_set_horizon_start,
  * qilqr_sharded_set_horizon_start, qilqr_shift_batch, qilqr_shift_batch_device, QILQR_STATE, QILQR_TAIL_HOLD, QILQR_TAIL_HOVER,
- * qilqr_backwards_pass_device, qilqr_closed_loop, qilqr_closed_loop_device and QILQR_CL_STATS were added within version 7: no structure changed. */
+ * qilqr_backwards_pass_device, qilqr_closed_loop, qilqr_closed_loop_device, QILQR_CL_STATS, qilqr_closed_loop_scored,
+ * qilqr_closed_loop_scored_device, QILQR_WRENCH and QILQR_CL_SCORE were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

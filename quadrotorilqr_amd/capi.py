@@ -36,6 +36,8 @@ MAX_OBSTACLES = 64  # QILQR_MAX_OBSTACLES: spheres per handle (set_obstacles), a
 OBSTACLE_WORDS = 8  # QILQR_OBSTACLE_WORDS: {cx, cy, cz, vx, vy, vz, radius, weight} of a per-problem sphere (set_batch_obstacles)
 STATE = 13  # QILQR_STATE: words 1..13 of a knot, t(3), q w,x,y,z, v_lin(3), v_ang(3) (shift's x0)
 TAILS = {"hold": 0, "hover": 1}  # QILQR_TAIL_HOLD, QILQR_TAIL_HOVER: the control of the knots a shift appends
+CL_SCORE = 4  # QILQR_CL_SCORE: cost, min clearance, knot of the min clearance, knots in collision (closed_loop with score=True)
+WRENCH = 6  # QILQR_WRENCH: F_x, F_y, F_z (world frame, N), tau_x, tau_y, tau_z (body frame, N m) of a disturbance (closed_loop's wrench)
 CL_STATS = 4  # QILQR_CL_STATS: max position error, max rotation error, |dx| at the last knot, clamped (knot, rotor) pairs (closed_loop)
 
 # every symbol include/quadrotor_ilqr.h declares
@@ -48,6 +50,7 @@ EXPORTS = (
     "qilqr_set_state_weight_schedule", "qilqr_sharded_set_state_weight_schedule",
     "qilqr_set_horizon_start", "qilqr_sharded_set_horizon_start", "qilqr_shift_batch", "qilqr_shift_batch_device",
     "qilqr_backwards_pass_device", "qilqr_closed_loop", "qilqr_closed_loop_device",
+    "qilqr_closed_loop_scored", "qilqr_closed_loop_scored_device",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -124,6 +127,8 @@ def load():
         lib.qilqr_backwards_pass_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         for f in (lib.qilqr_closed_loop, lib.qilqr_closed_loop_device):
             f.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 2
+        for f in (lib.qilqr_closed_loop_scored, lib.qilqr_closed_loop_scored_device):
+            f.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3
         _lib = lib
     return _lib
 
@@ -675,12 +680,16 @@ class QuadrotorILQRBatch:
         if rc:
             _raise(rc)
 
-    def closed_loop(self, plan, gains, x0, i0=0, i1=None, traj=True, stats=True):
+    def closed_loop(self, plan, gains, x0, i0=0, i1=None, traj=True, stats=True, wrench=None, desired=None, score=False):
         """qilqr_closed_loop, host arrays: the law u = u_i + K_i (x (-) plan_i) of plan (B, n, 18) and gains (B, n, 52) flown from the
         states x0 (B, S, 13) -- or (B, 13): S = 1 -- over knots i0 .. i1 (i1 = None: n - 1) with the handle's step, thrust limits and
         per-problem models (B * S of them: model b S + j flies sample (b, j)).  Returns a dict: traj (B, S, n, 18), NaN outside knots
         i0 .. i1 (traj=True), and stats (B, S, 4): max position error, max rotation error, |dx| at knot i1, clamped (knot, rotor) pairs
-        (stats=True)."""
+        (stats=True).
+        wrench, desired, score (qilqr_closed_loop_scored; without any of them the call is qilqr_closed_loop): wrench (B, S, n_w, 6) -- or
+        (B, S, 6): n_w = 1 -- with n_w 1 or n, {F world frame, tau body frame} held over each step; score=True adds score (B, S, 4): the
+        handle's cost of the flown knots i0 .. i1, the smallest clearance to any sphere of the handle's two tables, its knot, and the
+        number of knots in collision; desired (B, n, 18): the cost is taken against it instead of the handle's desired trajectory."""
         plan, gains, x0 = _d16(plan), _d16(gains), _d16(x0)
         if plan.ndim != 3 or plan.shape[2] != KNOT:
             raise TypeError("plan must be (B, n, 18)")
@@ -696,17 +705,39 @@ class QuadrotorILQRBatch:
         out_traj = _d16(np.full((B, S, n, KNOT), np.nan)) if traj else None
         out_stats = _d16(np.zeros((B, S, CL_STATS))) if stats else None
         vp = lambda a: C.c_void_p(0 if a is None else a.ctypes.data)
-        rc = load().qilqr_closed_loop(self._h, vp(plan), vp(gains), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1),
-                                      vp(out_traj), vp(out_stats))
+        if wrench is None and desired is None and not score:
+            rc = load().qilqr_closed_loop(self._h, vp(plan), vp(gains), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1),
+                                          vp(out_traj), vp(out_stats))
+            if rc:
+                _raise(rc)
+            return {k: v for k, v in (("traj", out_traj), ("stats", out_stats)) if v is not None}
+        n_w = 1
+        if wrench is not None:
+            wrench = _d16(wrench)
+            if wrench.ndim == 3:
+                wrench = wrench.reshape(wrench.shape[0], wrench.shape[1], 1, wrench.shape[2])
+            if wrench.ndim != 4 or wrench.shape[:2] != (B, S) or wrench.shape[3] != WRENCH:
+                raise TypeError(f"wrench must be ({B}, {S}, n_w, {WRENCH}) with n_w 1 or n")
+            n_w = wrench.shape[2]
+        if desired is not None:
+            desired = _d16(desired)
+            if desired.shape != (B, n, KNOT):
+                raise TypeError(f"desired must be ({B}, {n}, {KNOT}): one desired trajectory per plan")
+        out_score = _d16(np.zeros((B, S, CL_SCORE))) if score else None
+        rc = load().qilqr_closed_loop_scored(self._h, vp(plan), vp(gains), vp(x0), vp(wrench), C.c_int32(n_w), vp(desired), C.c_int32(B), C.c_int32(n),
+                                             C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1), vp(out_traj), vp(out_stats), vp(out_score))
         if rc:
             _raise(rc)
-        return {k: v for k, v in (("traj", out_traj), ("stats", out_stats)) if v is not None}
+        return {k: v for k, v in (("traj", out_traj), ("stats", out_stats), ("score", out_score)) if v is not None}
 
-    def closed_loop_device(self, plan, gains, x0, out_traj=None, out_stats=None, i0=0, i1=None, wait_current_stream=True):
+    def closed_loop_device(self, plan, gains, x0, out_traj=None, out_stats=None, i0=0, i1=None, wait_current_stream=True, wrench=None, desired=None,
+                           out_score=None):
         """qilqr_closed_loop_device on torch tensors, checked like shift_device: plan (B, n, 18), gains (B, n, 52), x0 (B, S, 13), out_traj
         (B, S, n, 18) or None, out_stats (B, S, 4) or None, float64, contiguous, on the solver's device.  Only knots i0 .. i1 of out_traj
         are written.  ENQUEUED on the solver's own stream -- behind whatever torch has enqueued on its current stream
-        (wait_current_stream) -- and not waited for: stream ordering as for shift_device."""
+        (wait_current_stream) -- and not waited for: stream ordering as for shift_device.
+        wrench (B, S, n_w, 6), desired (B, n, 18) and out_score (B, S, 4), checked like the others, make the call
+        qilqr_closed_loop_scored_device (closed_loop's docstring); without any of them it is qilqr_closed_loop_device."""
         if plan is None or plan.dim() != 3 or plan.shape[2] != KNOT:
             raise TypeError("plan must be (B, n, 18)")
         B, n = int(plan.shape[0]), int(plan.shape[1])
@@ -718,11 +749,22 @@ class QuadrotorILQRBatch:
                               (out_traj, "out_traj", (B, S, n, KNOT)), (out_stats, "out_stats", (B, S, CL_STATS))))
         if gains is None:
             raise TypeError("gains must be a (B, n, 52) tensor")
+        n_w = 1
+        if wrench is not None:
+            if wrench.dim() != 4:
+                raise TypeError(f"wrench must be ({B}, {S}, n_w, {WRENCH}) with n_w 1 or n")
+            n_w = int(wrench.shape[2])
+        self._device_tensors(((wrench, "wrench", (B, S, n_w, WRENCH)), (desired, "desired", (B, n, KNOT)), (out_score, "out_score", (B, S, CL_SCORE))))
         if wait_current_stream:
             self._wait_current_stream(plan)
         vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-        rc = load().qilqr_closed_loop_device(self._h, vp(plan), vp(gains), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)),
-                                             C.c_int32(i1), vp(out_traj), vp(out_stats))
+        if wrench is None and desired is None and out_score is None:
+            rc = load().qilqr_closed_loop_device(self._h, vp(plan), vp(gains), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)),
+                                                 C.c_int32(i1), vp(out_traj), vp(out_stats))
+        else:
+            rc = load().qilqr_closed_loop_scored_device(self._h, vp(plan), vp(gains), vp(x0), vp(wrench), C.c_int32(n_w), vp(desired), C.c_int32(B),
+                                                        C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1), vp(out_traj), vp(out_stats),
+                                                        vp(out_score))
         if rc:
             _raise(rc)
 

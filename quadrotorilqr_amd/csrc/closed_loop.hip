@@ -49,4 +49,6 @@ extern "C" int qilqr_debug_set_closed_loop_form(int32_t form) {
   qilqr::g_force_form = form < 0 ? -1 : (form != 0);
   return 0;
 }
+// (what closed_loop_scored.hip's launch reads, so that one switch forces both kernels' form)
+extern "C" int qilqr_debug_closed_loop_form(void) { return qilqr::g_force_form; }
 #endif

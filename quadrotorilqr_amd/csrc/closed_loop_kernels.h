@@ -20,10 +20,27 @@
 //   flattened (every other S; S = 1 is the policy evaluation of mpc.RecedingHorizon.control): a lane per (b, j), per-lane loads.
 // Part of closed_loop.hip's translation unit (gfx950 only); the per-sample routine is QILQR_HD and compiles under g++
 // (tests/host_closed_loop_harness.cpp).
+//
+// THE SCORED FLIGHT (qilqr_closed_loop_scored[_device]; k_closed_loop_scored, compiled by closed_loop_scored.hip): two compile-time switches
+// of the same routine.  With both off it is the routine above, statement for statement.
+//   WRENCH: a disturbance {F (world frame, N), tau (body frame, N m)} per sample, constant or one row per step, held over the step from
+//       knot i to i + 1.  It enters the body acceleration where thrust and moment do (cl_disturbed_acceleration: the order of the added
+//       operations is written there, once, for both integrators and both forms).  Per lane: three sixteen-byte loads per knot.
+//   SCORE: per sample {cost, min_clearance, knot_of_min_clearance, knots_in_collision} over knots i0 .. i1.  At knot i, after the law, the
+//       clamp, the statistics and the trajectory store and BEFORE the step (the cost's temporaries are dead when the step's become live):
+//           kc = knot_cost(Q_i, R, {flown state, applied control}, desired_i)      (se3_math.h, as it is: the general form, any Q)
+//           for the shared spheres, then the problem's own, each in index order:   (cl_score_sphere: add_sphere's value terms restated,
+//               h = radius - |p - c|;  if h > 0: kc += (weight h) h;                 because the clearance needs h of an inactive sphere too)
+//               clear = min(clear, -h)                                              (-h is |p - c| - radius exactly)
+//           cost += kc;  the smallest clearance so far, its knot (the first on ties) and the count of knots with clear < 0 follow.
+//       The operands of the score that are the same for every sample of a plan -- the desired knot, the knot's state weights, the shared
+//       sphere table and the plan's row of the per-problem table -- are wave-uniform in the shared-operand form: they join the LDS image
+//       (ClSharedScoreFetch), the desired knot and a scheduled Q double-buffered beside the plan knot, the rest written once.
 #pragma once
 
 #include "batch_models.h"
 #include "box_qp.h"
+#include "obstacles.h"
 #include "se3_math.h"
 
 // (as in se3_math.h: a * b + c fuses where the source says so and nowhere else, so that the law and the step have rollout_problem's bits)
@@ -115,12 +132,144 @@ QILQR_HD void closed_loop_law(const double pt[18], const double K[48], const dou
   }
 }
 
+// ---- the scored flight: what the two switches of closed_loop_sample read
+constexpr int CL_WRENCH = 6;  // words of a wrench: F_x, F_y, F_z (world frame), tau_x, tau_y, tau_z (body frame)
+constexpr int CL_SCORE = 4;   // words of a sample's score
+
+// where knot i's operands of the score are read from (global memory, or the block's LDS image)
+struct ClKnotScore {
+  const double *pd;  // the desired knot, 18 words
+  const double *Q;   // the knot's state weights, 12 x 12 row-major
+};
+// the two sphere tables as one sample reads them
+struct ClSpheres {
+  const double *shared;  // [n_shared][OB_WORDS]
+  int n_shared;
+  const double *own;     // word 0 of sphere 0 of the sample's problem: word w of sphere j is own[j * ss + w * ws]
+  int n_own, ws, ss;
+};
+// one sample's part of a scored flight
+struct ClSampleExtras {
+  const double *wrench;  // the sample's first row (WRENCH), 16-byte aligned
+  int wrench_step;       // doubles between the rows of successive knots: 0 (one wrench for the flight) or CL_WRENCH
+  ClSpheres spheres;     // (SCORE)
+  double *score;         // the sample's CL_SCORE words, or null: nothing is stored (SCORE)
+  // the running score (SCORE).  Kept here, not in locals of closed_loop_sample: a declaration there, even of nothing, reorders the
+  // routine's stack slots and with them the instructions of the instantiations that do not score.
+  double cost = 0.0, clear = HUGE_VAL;
+  int clear_knot = -1, hits = 0;
+};
+
+// The body acceleration under a wrench w = {F, tau}, held over the step.  body_acceleration[_fast] with two added operations, in this
+// order (R = R(q) of the state the acceleration is evaluated at, quat_to_R; every line one rounding sequence, nothing fused across lines):
+//     f[k]       = R[0][k] F_x + R[1][k] F_y + R[2][k] F_z          (mat3_tvec: R^T F, the velocities are body-frame)
+//     acc_lin[k] = a[k] + f[k] / mass                               (a[k]: the undisturbed value, formed first)
+//     rhs[k]     = (M[k] - (w x I w)[k]) + tau[k]                   (then inertia_inv rhs, as before)
+// FAST: the gravity terms as body_acceleration_fast forms them (the Euler step), else from R (the Runge-Kutta stages).  A zero wrench
+// leaves every value what it was (x + 0 = x).
+template <bool FAST>
+QILQR_HD void cl_disturbed_acceleration(const ModelConsts<double> &c, const double q[4], const double v[6], const double u[4], const double w[6],
+                                        double acc[6]) {
+  double R[9], f[3];
+  quat_to_R(q, R);
+  mat3_tvec(R, w, f);
+  double r6 = R[6], r7 = R[7], r8 = R[8];
+  if (FAST) {
+    const double x = q[0], y = q[1], z = q[2], qw = q[3];
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+    r6 = tz * x - ty * qw;
+    r7 = tz * y + tx * qw;
+    r8 = 1.0 - (tx * x + ty * y);
+  }
+  const double usum = ((u[0] + u[1]) + u[2]) + u[3];
+  const double a0 = -c.g * r6, a1 = -c.g * r7, a2 = -c.g * r8 + usum / c.mass;
+  const double f0 = f[0] / c.mass, f1 = f[1] / c.mass, f2 = f[2] / c.mass;
+  acc[0] = a0 + f0;
+  acc[1] = a1 + f1;
+  acc[2] = a2 + f2;
+  double M[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) M[i] = c.arms[4 * i] * u[0] + c.arms[4 * i + 1] * u[1] + c.arms[4 * i + 2] * u[2] + c.arms[4 * i + 3] * u[3];
+  const double *om = v + 3;
+  double Iw[3], wIw[3], rhs[3];
+  mat3_vec(c.inertia, om, Iw);
+  cross3(om, Iw, wIw);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double r = M[i] - wIw[i];
+    rhs[i] = r + w[3 + i];
+  }
+  mat3_vec(c.inertia_inv, rhs, acc + 3);
+}
+// rk4_step's state update (se3_math.h, without the Jacobians) with the wrench held over the four stages; R is each stage's own attitude
+QILQR_HD void cl_rk4_step_wrench(const ModelConsts<double> &c, double t[3], double q[4], double v[6], const double u[4], const double w[6]) {
+  const double coeffs[4] = {1.0 / 6.0, 2.0 / 6.0, 2.0 / 6.0, 1.0 / 6.0};
+  const double hs[4] = {0.0, c.dt / 2.0, c.dt / 2.0, c.dt};
+  double k[12], xdot[12];
+  for (int e = 0; e < 12; ++e) { k[e] = 0.0; xdot[e] = 0.0; }
+  for (int i = 0; i < 4; ++i) {
+    double tau[6], ti[3], qi[4], vi[6], acc[6];
+    for (int a = 0; a < 6; ++a) tau[a] = hs[i] * k[a];
+    se3_rplus(t, q, tau, ti, qi);
+    for (int a = 0; a < 6; ++a) vi[a] = v[a] + hs[i] * k[6 + a];
+    cl_disturbed_acceleration<false>(c, qi, vi, u, w, acc);
+    for (int a = 0; a < 6; ++a) { k[a] = vi[a]; k[6 + a] = acc[a]; }
+    for (int e = 0; e < 12; ++e) xdot[e] += coeffs[i] * k[e];
+  }
+  double tau[6], tn[3], qn[4];
+  for (int a = 0; a < 6; ++a) tau[a] = c.dt * xdot[a];
+  se3_rplus(t, q, tau, tn, qn);
+  for (int i = 0; i < 3; ++i) t[i] = tn[i];
+  for (int i = 0; i < 4; ++i) q[i] = qn[i];
+  for (int a = 0; a < 6; ++a) v[a] = v[a] + c.dt * xdot[6 + a];
+}
+
+// One sphere {cx, cy, cz, radius, weight} at the flown knot pt: add_sphere's (obstacles.h) distance, h and cost term, word for word, without
+// the differentials -- and the clearance -h = |p - c| - radius of EVERY sphere, active or not, into the knot's minimum.  A weight of 0
+// adds (0 h) h = +0 to the cost: its bits stay.  A NaN clearance is taken (the comparison fails), as the maxima of the statistics take one.
+QILQR_HD void cl_score_sphere(const double sp[OB_WORDS], const double *pt, double &cost, double &clear) {
+  const double e[3] = {pt[1] - sp[OB_CX], pt[2] - sp[OB_CX + 1], pt[3] - sp[OB_CX + 2]};
+  const double d = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+  const double h = sp[OB_RADIUS] - d;
+  const double cl = -h;
+  if (!(cl >= clear)) clear = cl;
+  if (!(h > 0.0)) return;
+  const double w = sp[OB_WEIGHT];
+  cost += (w * h) * h;
+}
+// the sphere terms of one knot at time ts: the shared table, then the problem's own spheres at fma(ts, v, c) (add_moving_sphere's centre)
+QILQR_HD void cl_score_spheres(const ClSpheres &s, double ts, const double *pt, double &cost, double &clear) {
+  for (int j = 0; j < s.n_shared; ++j) {
+    const double *sp = s.shared + j * OB_WORDS;
+    const double s5[OB_WORDS] = {sp[0], sp[1], sp[2], sp[3], sp[4]};
+    cl_score_sphere(s5, pt, cost, clear);
+  }
+  for (int j = 0; j < s.n_own; ++j) {
+    const double *sp = s.own + (long)j * s.ss;
+    const int ws = s.ws;
+    const double s5[OB_WORDS] = {fma(ts, sp[OB_BV * ws], sp[0]), fma(ts, sp[(OB_BV + 1) * ws], sp[ws]), fma(ts, sp[(OB_BV + 2) * ws], sp[2 * ws]),
+                                 sp[OB_BRADIUS * ws], sp[OB_BWEIGHT * ws]};
+    cl_score_sphere(s5, pt, cost, clear);
+  }
+}
+
+// the operands of a scored knot by per-lane (or host) loads: ClFlatFetch, and where the desired knot and the state weights of knot i lie
+struct ClFlatScoreFetch {
+  ClFlatFetch base;
+  const double *desired;  // the first desired knot of the window: the plan's own, or the handle's at its horizon start
+  const double *q;        // knot i's state weights are q + i * q_step (q_step = 0: the handle's Q at every knot)
+  long q_step;
+  QILQR_HD void operator()(int i, double pt[18], double K[48]) const { base(i, pt, K); }
+  QILQR_HD ClKnotScore score(int i) const { return ClKnotScore{desired + (long)i * 18, q + (long)i * q_step}; }
+};
+
 // One sample: x0 points at its 13 words, out at its first knot (or null: no trajectory store is issued), stats at its 4 words (or null).
 // c: the sample's model.  LIM: the control is clamped to [lo, hi] rotor by rotor, and the clamped control is what is stored and stepped
 // with, as in rollout_problem<.., LIM>.  fetch(i, pt, K) is called once per knot, i0 .. i1 in order, by every caller of one block alike.
-template <int INTEG, bool LIM, typename Fetch>
+// WRENCH, SCORE: the scored flight (above); ex is read only with one of them, fetch.score(i) only with SCORE.
+template <int INTEG, bool LIM, typename Fetch, bool WRENCH = false, bool SCORE = false>
 QILQR_HD void closed_loop_sample(const ModelConsts<double> &c, Fetch &fetch, const double *x0, int i0, int i1, double *out, double *stats,
-                                 const double *lo = nullptr, const double *hi = nullptr) {
+                                 const double *lo = nullptr, const double *hi = nullptr, ClSampleExtras *ex = nullptr) {
   double t[3] = {x0[0], x0[1], x0[2]};
   double q[4] = {x0[4], x0[5], x0[6], x0[3]};
   double v[6];
@@ -166,7 +315,39 @@ QILQR_HD void closed_loop_sample(const ModelConsts<double> &c, Fetch &fetch, con
 #pragma unroll
       for (int e = 0; e < 9; ++e) cl_store_pair(out + (long)i * 18 + 2 * e, o[2 * e], o[2 * e + 1]);
     }
-    if (i < i1) {
+    if constexpr (SCORE) {
+      const ClKnotScore ks = fetch.score(i);
+      const double o[18] = {pt[0], t[0], t[1], t[2], q[3], q[0], q[1], q[2], v[0], v[1], v[2], v[3], v[4], v[5], u[0], u[1], u[2], u[3]};
+      double edx[12], edu[4], sq[12], su[4];
+      double kc = knot_cost<false, double, false>(ks.Q, c.R, o, ks.pd, edx, edu, sq, su);
+      double kmin = HUGE_VAL;
+      cl_score_spheres(ex->spheres, (double)i * c.dt, o, kc, kmin);
+      ex->cost += kc;
+      if (!(kmin >= ex->clear)) {  // (the first knot on ties; a NaN is taken)
+        ex->clear = kmin;
+        ex->clear_knot = i;
+      }
+      ex->hits += kmin < 0.0 ? 1 : 0;
+    }
+    if constexpr (WRENCH) {
+      if (i < i1) {
+        double w[CL_WRENCH];
+        const double *wp = ex->wrench + (long)i * ex->wrench_step;
+#pragma unroll
+        for (int e = 0; e < CL_WRENCH / 2; ++e) cl_load_pair(wp + 2 * e, w[2 * e], w[2 * e + 1]);
+        if (INTEG == 1) {
+          cl_rk4_step_wrench(c, t, q, v, u, w);
+        } else {
+          double acc[6], tau[6];
+          cl_disturbed_acceleration<true>(c, q, v, u, w, acc);
+#pragma unroll
+          for (int a = 0; a < 6; ++a) tau[a] = c.dt * v[a];  // pose integrates with the OLD velocity
+          se3_rplus_fast(t, q, tau, sr);
+#pragma unroll
+          for (int a = 0; a < 6; ++a) v[a] = v[a] + c.dt * acc[a];
+        }
+      }
+    } else if (i < i1) {
       if (INTEG == 1) {
         rk4_step(c, t, q, v, u, (double *)nullptr);
       } else {
@@ -183,6 +364,12 @@ QILQR_HD void closed_loop_sample(const ModelConsts<double> &c, Fetch &fetch, con
   if (stats) {
     cl_store_pair(stats, sqrt(pos2), sqrt(ang2));
     cl_store_pair(stats + 2, sqrt(last2), (double)clamped);
+  }
+  if constexpr (SCORE) {
+    if (ex->score) {
+      cl_store_pair(ex->score, ex->cost, ex->clear);
+      cl_store_pair(ex->score + 2, (double)ex->clear_knot, (double)ex->hits);
+    }
   }
 }
 

@@ -454,4 +454,121 @@ int qilqr_closed_loop(qilqr_solver *s, const double *plan, const double *gains, 
   if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("qilqr_closed_loop: ") + hipGetErrorString(e));
   return QILQR_OK;
 }
+
+// ---- the scored flight: k_closed_loop_scored (closed_loop_scored_kernels.h, compiled by closed_loop_scored.hip) on the caller's arrays
+namespace {
+// what both forms refuse (closed_loop_launch.h: closed_loop_scored_refusal; the pointers are the caller's, host or device ones)
+int closed_loop_scored_refuse(const qilqr_solver *s, const double *plan, const double *gains, const double *x0, const double *wrench, int32_t n_w,
+                              const double *desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1, const double *out_traj,
+                              const double *out_stats, const double *out_score) {
+  const ClosedLoopCall base{plan, gains, x0, out_traj, out_stats, B, n, S, i0, i1, s != nullptr, s && s->f32, s && s->modeled, s ? s->models_B : 0, out_score};
+  const ClosedLoopScoredCall call{base, wrench, desired, n_w, s ? s->pobs_B : 0, s ? s->n_desired : 0, s ? s->n_sched : 0, s ? s->k0 : 0};
+  bool length = false;
+  const char *why = closed_loop_scored_refusal(call, &length);
+  if (!why) return QILQR_OK;
+  std::string text = why;
+  if (length)
+    return fail(QILQR_ERR_LENGTH_MISMATCH, text + " (i1 = " + std::to_string(i1) + ", horizon start " + std::to_string(s->k0) + ", desired trajectory of " +
+                                               std::to_string(s->n_desired) + " knots" + (s->n_sched > 0 ? ", schedule of " + std::to_string(s->n_sched) : std::string()) + ")");
+  if (s && s->modeled && !s->f32 && s->models_B != (long)B * S) text += ": they were set for " + std::to_string(s->models_B) + ", this call has B * S = " + std::to_string((long)B * S);
+  return fail(QILQR_ERR_INVALID_ARG, text);
+}
+int closed_loop_scored_enqueue(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0, const double *d_wrench, int32_t n_w,
+                               const double *d_desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1, double *d_out_traj, double *d_out_stats,
+                               double *d_out_score) {
+  ClosedLoopScoredLaunch call{};
+  call.base = ClosedLoopLaunch{d_plan, d_gains, d_x0, d_out_traj, d_out_stats, B, n, S, i0, i1, s->integrator, s->limited ? &s->limits : nullptr,
+                              s->modeled ? s->d_models : nullptr};
+  call.d_wrench = d_wrench;
+  call.n_w = n_w;
+  call.d_out_score = d_out_score;
+  if (d_out_score) {
+    call.d_desired = d_desired ? d_desired : (const double *)s->d_desired + 18 * (size_t)s->k0;
+    call.desired_step = d_desired ? 18l * n : 0;
+    if (s->n_sched > 0) {
+      call.d_q = s->d_qsched + (size_t)SCHED_WORDS * s->k0;
+      call.q_step = SCHED_WORDS;
+    } else {
+      if (!s->d_cl_q) {  // (Q lies 8 bytes off a 16-byte boundary inside ModelConsts: a copy of its own, made once; the handle's Q never changes)
+        HIP_TRY(hipMalloc((void **)&s->d_cl_q, sizeof(double) * 144));
+        HIP_TRY(hipMemcpyAsync(s->d_cl_q, s->consts.Q, sizeof(double) * 144, hipMemcpyHostToDevice, s->stream));
+      }
+      call.d_q = s->d_cl_q;
+      call.q_step = 0;
+    }
+    call.d_shared = s->n_obstacles > 0 ? s->d_obstacles : nullptr;
+    call.n_shared = s->n_obstacles;
+    call.d_own = s->pobs_B > 0 ? s->d_pobs : nullptr;
+    call.d_own_counts = s->pobs_B > 0 ? s->d_pobs_counts : nullptr;
+    call.own_K = s->pobs_K;
+  }
+  const hipError_t e = launch_closed_loop_scored(s->stream, s->consts, call);
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_closed_loop_scored: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+}  // namespace
+
+static_assert(QILQR_CL_SCORE == 4 && QILQR_WRENCH == 6, "closed_loop_kernels.h and the C header agree on the words of a score and of a wrench");
+int qilqr_closed_loop_scored_device(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0, const double *d_wrench,
+                                    int32_t n_w, const double *d_desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1,
+                                    double *d_out_traj, double *d_out_stats, double *d_out_score) {
+  int rc = closed_loop_scored_refuse(s, d_plan, d_gains, d_x0, d_wrench, n_w, d_desired, B, n, S, i0, i1, d_out_traj, d_out_stats, d_out_score);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return closed_loop_scored_enqueue(s, d_plan, d_gains, d_x0, d_wrench, n_w, d_desired, B, n, S, i0, i1, d_out_traj, d_out_stats, d_out_score);  // (not waited for)
+}
+
+int qilqr_closed_loop_scored(qilqr_solver *s, const double *plan, const double *gains, const double *x0, const double *wrench, int32_t n_w,
+                             const double *desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1, double *out_traj, double *out_stats,
+                             double *out_score) {
+  int rc = closed_loop_scored_refuse(s, plan, gains, x0, wrench, n_w, desired, B, n, S, i0, i1, out_traj, out_stats, out_score);
+  if (rc) return rc;
+  for (long r = 0; r < (long)B * S; ++r) {  // as qilqr_closed_loop checks them
+    const double *q = x0 + r * QILQR_STATE + 3;
+    const double nn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (!(std::fabs(nn - 1.0) <= 1e-10))
+      return fail(QILQR_ERR_BAD_QUATERNION, "x0: quaternion not normalized at problem " + std::to_string(r / S) + ", sample " + std::to_string(r % S));
+  }
+  if (wrench)
+    for (long r = 0; r < (long)B * S; ++r)
+      for (long k = 0; k < n_w; ++k)
+        for (int w = 0; w < QILQR_WRENCH; ++w)
+          if (!std::isfinite(wrench[(r * n_w + k) * QILQR_WRENCH + w]))
+            return fail(QILQR_ERR_INVALID_ARG, "wrench: a non-finite value at problem " + std::to_string(r / S) + ", sample " + std::to_string(r % S) + ", knot " +
+                                                   std::to_string(k));
+  HIP_TRY(hipSetDevice(s->device));
+  struct Scratch {  // freed on every return path
+    double *p = nullptr;
+    ~Scratch() {
+      if (p) (void)hipFree(p);
+    }
+  } scratch;
+  // (every count but x0's is even, and x0 goes last: each array starts on 16 bytes)
+  const size_t samples = (size_t)B * S, pc = 18 * (size_t)B * n, gc = 52 * (size_t)B * n, xc = (size_t)QILQR_STATE * samples;
+  const size_t tc = out_traj ? 18 * samples * n : 0, sc = out_stats ? QILQR_CL_STATS * samples : 0, oc = out_score ? QILQR_CL_SCORE * samples : 0;
+  const size_t wc = wrench ? QILQR_WRENCH * samples * (size_t)n_w : 0, dc = desired ? pc : 0;
+  HIP_TRY(hipMalloc((void **)&scratch.p, sizeof(double) * (pc + gc + tc + sc + oc + wc + dc + xc)));
+  double *d_plan = scratch.p, *d_gains = d_plan + pc, *d_traj = d_gains + gc, *d_stats = d_traj + tc, *d_score = d_stats + sc, *d_wrench = d_score + oc,
+         *d_desired = d_wrench + wc, *d_x0 = d_desired + dc;
+  HIP_TRY(hipMemcpyAsync(d_plan, plan, sizeof(double) * pc, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d_gains, gains, sizeof(double) * gc, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d_x0, x0, sizeof(double) * xc, hipMemcpyHostToDevice, s->stream));
+  if (wrench) HIP_TRY(hipMemcpyAsync(d_wrench, wrench, sizeof(double) * wc, hipMemcpyHostToDevice, s->stream));
+  if (desired) HIP_TRY(hipMemcpyAsync(d_desired, desired, sizeof(double) * dc, hipMemcpyHostToDevice, s->stream));
+  hipError_t e = hipSuccess;
+  if ((rc = closed_loop_scored_enqueue(s, d_plan, d_gains, d_x0, wrench ? d_wrench : nullptr, n_w, desired ? d_desired : nullptr, B, n, S, i0, i1,
+                                       out_traj ? d_traj : nullptr, out_stats ? d_stats : nullptr, out_score ? d_score : nullptr)) == QILQR_OK) {
+    const size_t pitch = sizeof(double) * 18 * (size_t)n, off = 18 * (size_t)i0;
+    if (out_traj)
+      e = hipMemcpy2DAsync(out_traj + off, pitch, d_traj + off, pitch, sizeof(double) * 18 * (size_t)(i1 - i0 + 1), samples, hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess && out_stats) e = hipMemcpyAsync(out_stats, d_stats, sizeof(double) * sc, hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess && out_score) e = hipMemcpyAsync(out_score, d_score, sizeof(double) * oc, hipMemcpyDeviceToHost, s->stream);
+  }
+  const hipError_t drained = hipStreamSynchronize(s->stream);  // (the copies read and write the caller's arrays, the kernel the scratch: finished before either goes)
+  if (rc) return rc;
+  if (e == hipSuccess) e = drained;
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("qilqr_closed_loop_scored: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
 }  // extern "C"

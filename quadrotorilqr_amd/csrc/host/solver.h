@@ -40,6 +40,7 @@ struct qilqr_solver {
   RecLayout layout;        // knot record layout chosen from the structure of Q
   void *d_desired = nullptr;    // shared desired trajectory, storage precision
   void *d_ctab = nullptr;       // constant operand table of k_backward, storage precision
+  double *d_cl_q = nullptr;     // the handle's Q on a 16-byte boundary (qilqr_closed_loop_scored without a schedule), allocated at the first scored call
   void *d_consts = nullptr;     // the model constants in device memory (k_linearize reads them where it uses them)
   bool f32 = false;             // mixed-precision mode (qilqr_device_config.precision == 1)
   int integrator = 0;           // 0 explicit Euler (the reference), 1 the Runge-Kutta extension (qilqr_set_integrator)

@@ -11,7 +11,9 @@ start advanced along its desired trajectory and schedule (set_horizon_start), an
 
 Between two ticks the plan can be flown closed loop: tick(x0, gains=True) also leaves the feedback gains about the new plan on the device
 (QuadrotorILQRBatch.backwards_pass_device), and control(x, i) evaluates the law u = u_i + K_i (x (-) plan_i) at measured states
-(closed_loop_device with one sample per plan and i0 = i1 = i).
+(closed_loop_device with one sample per plan and i0 = i1 = i); evaluate(x0, wrench) flies S sampled states per plan under that law -- and
+under sampled disturbances -- and returns the statistics and the score of every flight (closed_loop_device with out_score), on device
+buffers.
 """
 import numpy as np
 
@@ -39,6 +41,7 @@ class RecedingHorizon:
         self.gains = self.terms = None   # (B, n, 52), (B, 2): about the plan of the last solve while _have_gains
         self._have_gains = False
         self._xc = self._ctl = None      # control()'s states (B, 1, 13) and the knots it writes (B, 1, n, 18)
+        self._eval = None                # evaluate()'s buffers for the last S: (S, n_w, x0, wrench, stats, score)
 
     def _to_device(self, a, dst):
         import torch
@@ -97,6 +100,38 @@ class RecedingHorizon:
         # (enqueued on the solver's stream and not waited for: torch's stream waits for it before it reads the knot)
         torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
         return self._ctl[:, 0, i, 14:18].clone()
+
+    def evaluate(self, x0, wrench=None):
+        """The last plan's feedback law scored from sampled states: x0 (B, S, 13; NumPy or torch) flown over the whole horizon (knots
+        0 .. n - 1) under wrench (None, or (B, S, n_w, 6) with n_w 1 or n: QuadrotorILQRBatch.closed_loop's), at the handle's current
+        horizon start -- the one the plan was solved at.  Needs the gains of the last plan (start / tick with gains=True), as control()
+        does.  Returns {"stats": (B, S, 4), "score": (B, S, 4)}: device tensors this object owns (valid until the next evaluate with another
+        S), complete on torch's current stream.  No trajectory is written."""
+        import torch
+        if not self._have_gains:
+            raise RuntimeError("evaluate() needs the gains of the last plan: call start() or tick() with gains=True")
+        shape = tuple(x0.shape)
+        if len(shape) != 3 or shape[0] != self.B or shape[2] != capi.STATE:
+            raise TypeError(f"x0 must be ({self.B}, S, {capi.STATE})")
+        S = shape[1]
+        n_w = 0
+        if wrench is not None:
+            wshape = tuple(wrench.shape)
+            if len(wshape) != 4 or wshape[:2] != (self.B, S) or wshape[3] != capi.WRENCH:
+                raise TypeError(f"wrench must be ({self.B}, {S}, n_w, {capi.WRENCH})")
+            n_w = wshape[2]
+        if self._eval is None or self._eval[0] != S or self._eval[1] != n_w:
+            new = lambda *s: torch.zeros(s, dtype=torch.float64, device=self.device)
+            self._eval = (S, n_w, new(self.B, S, capi.STATE), new(self.B, S, n_w, capi.WRENCH) if n_w else None, new(self.B, S, capi.CL_STATS),
+                          new(self.B, S, capi.CL_SCORE))
+        _, _, d_x0, d_w, d_stats, d_score = self._eval
+        self._to_device(x0, d_x0)
+        if d_w is not None:
+            self._to_device(wrench, d_w)
+        self.solver.closed_loop_device(self._buf[self._cur], self.gains, d_x0, out_stats=d_stats, wrench=d_w, out_score=d_score)
+        # (enqueued on the solver's stream and not waited for: torch's stream waits for it before anything reads the results)
+        torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
+        return dict(stats=d_stats, score=d_score)
 
     def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False, gains=False):
         """One control tick: the horizon start advanced by `steps` (advance=False: the desired trajectory is relative to the vehicle and

@@ -205,3 +205,13 @@ def config3(B=8192, N=200, seed=3):
     cfg = config2(B=B, N=N, seed=seed)
     cfg["options"] = dict(cfg["options"], rtol=1e-5, atol=1e-5)
     return cfg
+
+
+def gust_wrenches(B, S, n_w, seed, force_sigma_n, torque_sigma_nm):
+    """(B, S, n_w, 6) disturbance wrenches for closed_loop(..., wrench=): zero-mean normal samples, seeded -- forces {F_x, F_y, F_z} in
+    newtons in the world frame with standard deviation force_sigma_n per axis, torques {tau_x, tau_y, tau_z} in N m in the body frame
+    with torque_sigma_nm.  n_w = 1: one wrench per sample for the whole flight; n_w = n: one per step, independent from step to step."""
+    w = np.random.default_rng(seed).standard_normal((int(B), int(S), int(n_w), 6))
+    w[..., 0:3] *= float(force_sigma_n)
+    w[..., 3:6] *= float(torque_sigma_nm)
+    return np.ascontiguousarray(w)

@@ -508,6 +508,55 @@ int qilqr_closed_loop_scored(qilqr_solver *s, const double *plan, const double *
                              int32_t n_w, const double *desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1,
                              double *out_traj, double *out_stats, double *out_score);
 
+/* The ends of the Monte-Carlo loop on the device (extension): what the scored flight reads is sampled, and what it writes is reduced,
+ * where it lies -- sample, fly, reduce are four enqueues on the handle's stream, the only host input the measured state of each plan,
+ * the only output QILQR_MC_SUMMARY words per plan.  Device arrays only; sharded handles have no such call (use a shard's solver).
+ *
+ * The normals.  Philox4x32-10 with counter {i, s0 + s, b0 + b, stream << 16 | j} and key {seed & 0xffffffff, seed >> 32}: i the row
+ * (knot), s the sample, b the plan, stream 0 for gusts and 1 for start states, j the pair of normals within the row.  Of the four output
+ * words w0..w3: u1 = ((w0 >> 5) 2^26 + (w1 >> 6) + 1) 2^-53 in (0, 1], t = ((w2 >> 5) 2^26 + (w3 >> 6)) 2^-53 in [0, 1),
+ * r = sqrt(-2 log u1), z0 = r cos(2 pi t), z1 = r sin(2 pi t).  A draw depends on (seed, b0 + b, s0 + s, i, stream, j) and on nothing
+ * else -- not on B, S or what else is in the batch: a call at (b0, s0) for a sub-block writes the bits of that slice of the whole.
+ *
+ * qilqr_sample_gusts_device writes d_wrench, B x S x n_w x QILQR_WRENCH -- the wrench array of qilqr_closed_loop_scored_device -- all
+ * n_w rows of it.  Component c of a flight is a stationary first-order Gauss-Markov process about mean[c] with deviation sigma[c] and
+ * correlation time tau_force_s (c < 3) or tau_torque_s: with rho = tau > 0 ? exp(-dt / tau) : 0 (dt the handle's) and
+ * kappa = sigma sqrt((1 - rho)(1 + rho)), computed on the host in double, and xi_i normal z(c % 2) of pair j = c / 2 of row i:
+ *     g_0 = sigma xi_0,   g_i = fma(rho, g_{i-1}, kappa xi_i),   wrench[b, s, i, c] = mean + g_i
+ * tau = 0 is white noise per step (mean + sigma xi_i); n_w = 1 is row 0 of any longer call.
+ *
+ * qilqr_sample_states_device writes d_x0, B x S x QILQR_STATE: x0[b, s] = x_nom[b] (+) delta with delta[c] = sigma12[c] xi_c over the 12
+ * tangent words in the solver's order [rho, theta, dv, dw] (stream 1, row 0, pairs 0..5), (+) the solver's state addition: the pose
+ * composed with Exp([rho; theta]) on the right, the two body velocities added.  d_x_nom is B x QILQR_STATE on the device, sigma12 12
+ * doubles on the host.  flags bit 0: sample s0 + s == 0 is x_nom[b] itself, word for word (an undisturbed baseline in every batch).
+ *
+ * qilqr_reduce_scores_device reads d_score, B x S x QILQR_CL_SCORE as the scored flight writes it, and writes d_summary,
+ * B x QILQR_MC_SUMMARY:
+ *     0  the mean cost over the samples whose cost is finite      4  the fraction of samples with knots_in_collision > 0
+ *     1  the population standard deviation of those costs          5  the smallest min_clearance (+inf without spheres; a NaN is skipped)
+ *     2  the largest finite cost                                   6  its sample, the smallest on ties; -1 if every one is +inf
+ *     3  its sample, the smallest on ties; -1 if none              7  the fraction of samples whose cost is not finite (diverged flights)
+ * Words 0 .. 2 are NaN when no cost is finite.  One wavefront reduces a plan: lane l folds samples l, l + 64, ... in order, the lanes
+ * are combined by the tree 32, 16, 8, 4, 2, 1, and the deviation is a second pass about the mean: a plan's bits depend on its S rows only.
+ *
+ * All three ENQUEUE on the handle's stream and do not drain it, with the ordering rules of qilqr_closed_loop_device, and need the
+ * handle for its stream, its device and its dt only: every precision mode is accepted.  QILQR_ERR_INVALID_ARG, before the device is
+ * touched, for a NULL pointer or model, a non-positive B, S or n_w, a negative b0 or s0, a device array off a 16-byte boundary, a
+ * negative or non-finite sigma or tau, a non-finite mean, unknown flag bits, d_x0 overlapping d_x_nom, d_summary overlapping d_score,
+ * and -- last -- a NULL handle. */
+#define QILQR_MC_SUMMARY 8
+typedef struct {
+  double mean[6];      /* N, N, N (world frame), N m, N m, N m (body frame) */
+  double sigma[6];     /* the stationary standard deviations */
+  double tau_force_s;  /* the correlation time of the three forces; 0: white noise per step */
+  double tau_torque_s; /* ... of the three torques */
+} qilqr_gust_model;
+int qilqr_sample_gusts_device(qilqr_solver *s, const qilqr_gust_model *m, uint64_t seed, int32_t B, int32_t S, int32_t n_w, int32_t b0,
+                              int32_t s0, double *d_wrench);
+int qilqr_sample_states_device(qilqr_solver *s, const double *d_x_nom, const double *sigma12, uint64_t seed, int32_t B, int32_t S,
+                               int32_t b0, int32_t s0, uint32_t flags, double *d_x0);
+int qilqr_reduce_scores_device(qilqr_solver *s, const double *d_score, int32_t B, int32_t S, double *d_summary);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -645,7 +694,8 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * QILQR_OBSTACLE_WORDS, qilqr_set_state_weight_schedule, qilqr_sharded_set_state_weight_schedule, qilqr_set_horizon_start,
  * qilqr_sharded_set_horizon_start, qilqr_shift_batch, qilqr_shift_batch_device, QILQR_STATE, QILQR_TAIL_HOLD, QILQR_TAIL_HOVER,
  * qilqr_backwards_pass_device, qilqr_closed_loop, qilqr_closed_loop_device, QILQR_CL_STATS, qilqr_closed_loop_scored,
- * qilqr_closed_loop_scored_device, QILQR_WRENCH and QILQR_CL_SCORE were added within version 7: no structure changed. */
+ * qilqr_closed_loop_scored_device, QILQR_WRENCH, QILQR_CL_SCORE, qilqr_sample_gusts_device, qilqr_sample_states_device,
+ * qilqr_reduce_scores_device, qilqr_gust_model and QILQR_MC_SUMMARY were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

@@ -38,6 +38,7 @@ STATE = 13  # QILQR_STATE: words 1..13 of a knot, t(3), q w,x,y,z, v_lin(3), v_a
 TAILS = {"hold": 0, "hover": 1}  # QILQR_TAIL_HOLD, QILQR_TAIL_HOVER: the control of the knots a shift appends
 CL_SCORE = 4  # QILQR_CL_SCORE: cost, min clearance, knot of the min clearance, knots in collision (closed_loop with score=True)
 WRENCH = 6  # QILQR_WRENCH: F_x, F_y, F_z (world frame, N), tau_x, tau_y, tau_z (body frame, N m) of a disturbance (closed_loop's wrench)
+MC_SUMMARY = 8  # QILQR_MC_SUMMARY: mean cost, its deviation, worst cost, its sample, collision fraction, min clearance, its sample, diverged fraction
 CL_STATS = 4  # QILQR_CL_STATS: max position error, max rotation error, |dx| at the last knot, clamped (knot, rotor) pairs (closed_loop)
 
 # every symbol include/quadrotor_ilqr.h declares
@@ -51,6 +52,7 @@ EXPORTS = (
     "qilqr_set_horizon_start", "qilqr_sharded_set_horizon_start", "qilqr_shift_batch", "qilqr_shift_batch_device",
     "qilqr_backwards_pass_device", "qilqr_closed_loop", "qilqr_closed_loop_device",
     "qilqr_closed_loop_scored", "qilqr_closed_loop_scored_device",
+    "qilqr_sample_gusts_device", "qilqr_sample_states_device", "qilqr_reduce_scores_device",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -76,6 +78,10 @@ class DeviceConfig(C.Structure):
                 ("streams", C.c_int32), ("persistent", C.c_int32), ("compaction", C.c_int32),
                 # ABI version 7: the A/B switches that were environment variables
                 ("round_launch", C.c_int32), ("rounds_per_launch", C.c_int32), ("fuse_in_flight", C.c_int32), ("dense_weights", C.c_int32)]
+
+
+class GustModel(C.Structure):
+    _fields_ = [("mean", C.c_double * 6), ("sigma", C.c_double * 6), ("tau_force_s", C.c_double), ("tau_torque_s", C.c_double)]
 
 
 class Profile(C.Structure):
@@ -129,6 +135,9 @@ def load():
             f.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 2
         for f in (lib.qilqr_closed_loop_scored, lib.qilqr_closed_loop_scored_device):
             f.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3
+        lib.qilqr_sample_gusts_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_int32] * 5 + [C.c_void_p]
+        lib.qilqr_sample_states_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_int32] * 4 + [C.c_uint32, C.c_void_p]
+        lib.qilqr_reduce_scores_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -273,6 +282,25 @@ def schedule_array(Qs):
         raise TypeError(f"state-weight schedule: an (n, 12, 12) array of per-knot Q, n >= 1; got shape {arr.shape} "
                         "(clear_state_weight_schedule() switches it off)")
     return arr
+
+
+def gust_model(sigma, mean=None, tau_force_s=0.0, tau_torque_s=0.0):
+    """a qilqr_gust_model: sigma and mean are 6 words {F_x, F_y, F_z, tau_x, tau_y, tau_z}, or two ({force, torque}: the same for x, y, z),
+    or one number for all six; tau 0 is white noise per step"""
+    def six(v, name):
+        v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        if v.shape == (1,):
+            v = np.repeat(v, 6)
+        elif v.shape == (2,):
+            v = np.repeat(v, 3)
+        if v.shape != (6,):
+            raise TypeError(f"{name} must have 1, 2 or 6 words")
+        return v
+    m = GustModel()
+    m.sigma[:] = six(sigma, "sigma")
+    m.mean[:] = six(0.0 if mean is None else mean, "mean")
+    m.tau_force_s, m.tau_torque_s = float(tau_force_s), float(tau_torque_s)
+    return m
 
 
 def _tail(tail):
@@ -765,6 +793,62 @@ class QuadrotorILQRBatch:
             rc = load().qilqr_closed_loop_scored_device(self._h, vp(plan), vp(gains), vp(x0), vp(wrench), C.c_int32(n_w), vp(desired), C.c_int32(B),
                                                         C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1), vp(out_traj), vp(out_stats),
                                                         vp(out_score))
+        if rc:
+            _raise(rc)
+
+    # ---- the ends of the Monte-Carlo loop: gusts and start states sampled, and scores reduced, on the device
+    def sample_gusts_device(self, out, seed, sigma, mean=None, tau_force_s=0.0, tau_torque_s=0.0, b0=0, s0=0, wait_current_stream=True):
+        """qilqr_sample_gusts_device: fills out (B, S, n_w, 6), a float64 tensor on the solver's device, with Gauss-Markov gusts of
+        deviation sigma about mean (gust_model's forms) and correlation times tau_force_s, tau_torque_s (0: white noise per step) -- the
+        wrench of closed_loop_device.  A word depends on (seed, b0 + b, s0 + s, knot, component) and the model alone.  ENQUEUED on the
+        solver's own stream and not waited for, as closed_loop_device."""
+        if out is None or out.dim() != 4:
+            raise TypeError(f"out must be (B, S, n_w, {WRENCH})")
+        B, S, n_w = (int(v) for v in out.shape[:3])
+        self._device_tensors(((out, "out", (B, S, n_w, WRENCH)),))
+        m = gust_model(sigma, mean, tau_force_s, tau_torque_s)
+        if wait_current_stream:
+            self._wait_current_stream(out)
+        rc = load().qilqr_sample_gusts_device(self._h, C.byref(m), C.c_uint64(int(seed)), C.c_int32(B), C.c_int32(S), C.c_int32(n_w), C.c_int32(int(b0)),
+                                              C.c_int32(int(s0)), C.c_void_p(out.data_ptr()))
+        if rc:
+            _raise(rc)
+
+    def sample_states_device(self, x_nom, out, seed, sigma, b0=0, s0=0, first_is_nominal=False, wait_current_stream=True):
+        """qilqr_sample_states_device: out[b, s] = x_nom[b] (+) sigma * xi, x_nom (B, 13) and out (B, S, 13) float64 tensors on the solver's
+        device, sigma 12 words over the tangent [rho, theta, dv, dw] (or one number for all).  first_is_nominal: sample s0 + s == 0 is
+        x_nom[b] itself.  ENQUEUED on the solver's own stream and not waited for."""
+        if out is None or out.dim() != 3:
+            raise TypeError(f"out must be (B, S, {STATE})")
+        B, S = int(out.shape[0]), int(out.shape[1])
+        self._device_tensors(((x_nom, "x_nom", (B, STATE)), (out, "out", (B, S, STATE))))
+        if x_nom is None:
+            raise TypeError(f"x_nom must be a ({B}, {STATE}) tensor")
+        sig = np.atleast_1d(np.asarray(sigma, dtype=np.float64))
+        sig = np.ascontiguousarray(np.repeat(sig, 12) if sig.shape == (1,) else sig)
+        if sig.shape != (12,):
+            raise TypeError("sigma must have 1 or 12 words")
+        if wait_current_stream:
+            self._wait_current_stream(out)
+        rc = load().qilqr_sample_states_device(self._h, C.c_void_p(x_nom.data_ptr()), C.c_void_p(sig.ctypes.data), C.c_uint64(int(seed)), C.c_int32(B),
+                                               C.c_int32(S), C.c_int32(int(b0)), C.c_int32(int(s0)), C.c_uint32(1 if first_is_nominal else 0),
+                                               C.c_void_p(out.data_ptr()))
+        if rc:
+            _raise(rc)
+
+    def reduce_scores_device(self, score, out, wait_current_stream=True):
+        """qilqr_reduce_scores_device: out (B, 8) from score (B, S, 4) as closed_loop_device's out_score holds it: mean cost, its deviation,
+        worst cost, its sample, the fraction in collision, the smallest clearance, its sample, the fraction that diverged.  ENQUEUED on
+        the solver's own stream and not waited for."""
+        if score is None or score.dim() != 3:
+            raise TypeError(f"score must be (B, S, {CL_SCORE})")
+        B, S = int(score.shape[0]), int(score.shape[1])
+        self._device_tensors(((score, "score", (B, S, CL_SCORE)), (out, "out", (B, MC_SUMMARY))))
+        if out is None:
+            raise TypeError(f"out must be a ({B}, {MC_SUMMARY}) tensor")
+        if wait_current_stream:
+            self._wait_current_stream(score)
+        rc = load().qilqr_reduce_scores_device(self._h, C.c_void_p(score.data_ptr()), C.c_int32(B), C.c_int32(S), C.c_void_p(out.data_ptr()))
         if rc:
             _raise(rc)
 

@@ -571,4 +571,48 @@ int qilqr_closed_loop_scored(qilqr_solver *s, const double *plan, const double *
   if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("qilqr_closed_loop_scored: ") + hipGetErrorString(e));
   return QILQR_OK;
 }
+
+// ---- the ends of the Monte-Carlo loop: k_sample_gusts, k_sample_states and k_reduce_scores (monte_carlo_kernels.h, compiled by
+// monte_carlo.hip) on the caller's device arrays.  The handle gives its stream, its device and its dt; the rules are monte_carlo_launch.h's.
+static_assert(QILQR_MC_SUMMARY == 8, "monte_carlo_kernels.h and the C header agree on the words of a plan's summary");
+int qilqr_sample_gusts_device(qilqr_solver *s, const qilqr_gust_model *m, uint64_t seed, int32_t B, int32_t S, int32_t n_w, int32_t b0, int32_t s0,
+                              double *d_wrench) {
+  SampleGustsCall call{s != nullptr, m != nullptr, d_wrench, B, S, n_w, b0, s0, {}, {}, m ? m->tau_force_s : 0.0, m ? m->tau_torque_s : 0.0};
+  for (int k = 0; k < 6; ++k) {
+    call.mean[k] = m ? m->mean[k] : 0.0;
+    call.sigma[k] = m ? m->sigma[k] : 0.0;
+  }
+  if (const char *why = sample_gusts_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
+  HIP_TRY(hipSetDevice(s->device));
+  SampleGustsLaunch go{d_wrench, B, S, n_w, b0, s0, seed, s->consts.dt, {}, {}, m->tau_force_s, m->tau_torque_s};
+  for (int k = 0; k < 6; ++k) {
+    go.mean[k] = m->mean[k];
+    go.sigma[k] = m->sigma[k];
+  }
+  const hipError_t e = launch_sample_gusts(s->stream, go);  // (enqueued on the handle's stream; not waited for)
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_sample_gusts: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+
+int qilqr_sample_states_device(qilqr_solver *s, const double *d_x_nom, const double *sigma12, uint64_t seed, int32_t B, int32_t S, int32_t b0,
+                               int32_t s0, uint32_t flags, double *d_x0) {
+  SampleStatesCall call{s != nullptr, sigma12 != nullptr, d_x_nom, d_x0, B, S, b0, s0, flags, {}};
+  for (int k = 0; k < 12; ++k) call.sigma[k] = sigma12 ? sigma12[k] : 0.0;
+  if (const char *why = sample_states_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
+  HIP_TRY(hipSetDevice(s->device));
+  SampleStatesLaunch go{d_x_nom, d_x0, B, S, b0, s0, flags, seed, {}};
+  for (int k = 0; k < 12; ++k) go.sigma[k] = sigma12[k];
+  const hipError_t e = launch_sample_states(s->stream, go);  // (not waited for)
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_sample_states: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+
+int qilqr_reduce_scores_device(qilqr_solver *s, const double *d_score, int32_t B, int32_t S, double *d_summary) {
+  const ReduceScoresCall call{s != nullptr, d_score, d_summary, B, S};
+  if (const char *why = reduce_scores_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
+  HIP_TRY(hipSetDevice(s->device));
+  const hipError_t e = launch_reduce_scores(s->stream, ReduceScoresLaunch{d_score, d_summary, B, S});  // (not waited for)
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_reduce_scores: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
 }  // extern "C"

@@ -33,6 +33,7 @@
 #include "horizon.h"
 #include "shift_launch.h"
 #include "closed_loop_launch.h"
+#include "monte_carlo_launch.h"
 
 using namespace qilqr;
 

@@ -42,6 +42,8 @@ class RecedingHorizon:
         self._have_gains = False
         self._xc = self._ctl = None      # control()'s states (B, 1, 13) and the knots it writes (B, 1, n, 18)
         self._eval = None                # evaluate()'s buffers for the last S: (S, n_w, x0, wrench, stats, score)
+        self._mc = None                  # evaluate_sampled()'s for the last (S, n_w): (S, n_w, x_nom, x0, wrench, stats, score, summary)
+        self.sampled = None              # ... and what its last call sampled: (x0 (B, S, 13), wrench (B, S, n_w, 6) or None), its buffers
 
     def _to_device(self, a, dst):
         import torch
@@ -132,6 +134,41 @@ class RecedingHorizon:
         # (enqueued on the solver's stream and not waited for: torch's stream waits for it before anything reads the results)
         torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
         return dict(stats=d_stats, score=d_score)
+
+    def evaluate_sampled(self, x, S, seed, state_sigma, gust=None, n_w=None, first_is_nominal=True):
+        """The Monte-Carlo loop about the last plan without the host: S start states per plan sampled about the measured states x (B, 13;
+        NumPy or torch) with deviations state_sigma (12 words over [rho, theta, dv, dw], or one number), gusts sampled from `gust` (None: no
+        disturbance; else a dict with the fields of qilqr_gust_model -- sigma, and optionally mean, tau_force_s, tau_torque_s) for n_w
+        knots (1, or n: the default), the law flown and scored over the whole horizon as evaluate() does, and the scores reduced per plan.
+        Four enqueues on the solver's stream, then torch's current stream waits once.  first_is_nominal: sample 0 starts at x itself.
+        Returns {"stats": (B, S, 4), "score": (B, S, 4), "summary": (B, 8)} (QuadrotorILQRBatch.reduce_scores_device's words): device
+        tensors this object owns, valid until the next call with another S or n_w.  The sampled states and wrenches stay in
+        `self.sampled` = (x0, wrench).  Needs the gains of the last plan, as evaluate()."""
+        import torch
+        if not self._have_gains:
+            raise RuntimeError("evaluate_sampled() needs the gains of the last plan: call start() or tick() with gains=True")
+        S = int(S)
+        if S <= 0:
+            raise TypeError("S must be positive")
+        n_w = 0 if gust is None else (self.n if n_w is None else int(n_w))
+        if gust is not None and n_w not in (1, self.n):
+            raise TypeError(f"n_w must be 1 or {self.n}")
+        if self._mc is None or self._mc[0] != S or self._mc[1] != n_w:
+            new = lambda *s: torch.zeros(s, dtype=torch.float64, device=self.device)
+            self._mc = (S, n_w, new(self.B, capi.STATE), new(self.B, S, capi.STATE), new(self.B, S, n_w, capi.WRENCH) if n_w else None,
+                        new(self.B, S, capi.CL_STATS), new(self.B, S, capi.CL_SCORE), new(self.B, capi.MC_SUMMARY))
+        _, _, d_nom, d_x0, d_w, d_stats, d_score, d_sum = self._mc
+        self._to_device(x, d_nom)  # (on torch's current stream: the first enqueue below makes the solver's stream wait for it)
+        self.solver.sample_states_device(d_nom, d_x0, seed, state_sigma, first_is_nominal=first_is_nominal)
+        if d_w is not None:
+            self.solver.sample_gusts_device(d_w, seed, gust["sigma"], gust.get("mean"), gust.get("tau_force_s", 0.0), gust.get("tau_torque_s", 0.0),
+                                            wait_current_stream=False)
+        self.solver.closed_loop_device(self._buf[self._cur], self.gains, d_x0, out_stats=d_stats, wrench=d_w, out_score=d_score, wait_current_stream=False)
+        self.solver.reduce_scores_device(d_score, d_sum, wait_current_stream=False)
+        # (all four enqueued on the solver's stream, in order, and none waited for: torch's stream waits once, behind the last)
+        torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
+        self.sampled = (d_x0, d_w)
+        return dict(stats=d_stats, score=d_score, summary=d_sum)
 
     def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False, gains=False):
         """One control tick: the horizon start advanced by `steps` (advance=False: the desired trajectory is relative to the vehicle and

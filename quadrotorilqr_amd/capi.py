@@ -175,6 +175,12 @@ def _raise(rc, ls_max_iters=None):
     raise RuntimeError(f"quadrotor_ilqr error {rc}: {msg}")
 
 
+def _check(rc, raiser=_raise):
+    """every call's return code goes through here: `raiser` turns one that is not OK into the exception"""
+    if rc:
+        raiser(rc)
+
+
 def _create_args(self, mass_kg, inertia, arm_length_m, torque_to_thrust_ratio_m, g_mpss, Q, R, desired, options, device, profile,
                  sync_every, force_general, single_wave_rollout, precision, streams, persistent, compaction=0, round_launch=0,
                  rounds_per_launch=0, fuse_in_flight=0, dense_weights=0):
@@ -316,6 +322,12 @@ def _raise_models(rc):
     _raise(rc)
 
 
+def _raise_regularisation(rc):
+    if rc == ERR_INVALID_ARG:
+        raise ValueError(load().qilqr_last_error().decode())
+    _raise(rc)
+
+
 def _batch_outputs(init, out):
     """result arrays of a batch solve: fresh, or the caller's (checked)"""
     B = init.shape[0]
@@ -345,7 +357,7 @@ class QuadrotorILQRBatch:
                                     C.c_double(dt_s), C.byref(o), C.byref(dc), C.c_size_t(C.sizeof(dc)), C.byref(self._h))
         if rc:
             self._h = None
-            _raise(rc)
+        _check(rc)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -368,10 +380,8 @@ class QuadrotorILQRBatch:
         dcost = np.zeros(max(cap, 1))
         dtraj = np.zeros((max(cap, 1), n, KNOT))
         cost, st, it, nd = C.c_double(), C.c_int32(), C.c_int32(), C.c_int32()
-        rc = load().qilqr_solve(self._h, _p(init), C.c_int32(n), _p(out), C.byref(cost), C.byref(st),
-                                C.byref(it), _p(dcost), _p(dtraj), C.c_int32(cap), C.byref(nd))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_solve(self._h, _p(init), C.c_int32(n), _p(out), C.byref(cost), C.byref(st),
+                                  C.byref(it), _p(dcost), _p(dtraj), C.c_int32(cap), C.byref(nd)))
         k = nd.value
         return out, dict(cost=cost.value, status=st.value, iters=it.value, debug_costs=dcost[:k].copy(),
                          debug_trajs=dtraj[:k].copy())
@@ -385,10 +395,8 @@ class QuadrotorILQRBatch:
         B, n = init.shape[0], init.shape[1]
         des = None if desired_batch is None else _d(desired_batch)
         out = _batch_outputs(init, out)
-        rc = load().qilqr_solve_batch(self._h, _p(init), _p(des), C.c_int32(B), C.c_int32(n), _p(out["traj"]), _p(out["cost"]),
-                                      _ip(out["status"]), _ip(out["iters"]), _ip(out["n_bwd"]), _ip(out["n_fwd"]))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_solve_batch(self._h, _p(init), _p(des), C.c_int32(B), C.c_int32(n), _p(out["traj"]), _p(out["cost"]),
+                                        _ip(out["status"]), _ip(out["iters"]), _ip(out["n_bwd"]), _ip(out["n_fwd"])))
         return out
 
     # ---- batch of problems, torch CUDA tensors already resident in HBM
@@ -404,49 +412,24 @@ class QuadrotorILQRBatch:
         if init.dim() != 3 or init.shape[2] != KNOT:
             raise TypeError("init must be (B, n, 18)")
         B, n = int(init.shape[0]), int(init.shape[1])
-        dev_index = load().qilqr_device(self._h)
-
-        def check(t, name, dtype, shape):
-            if t is None:
-                return
-            if not t.is_cuda or t.device.index != dev_index:
-                raise TypeError(f"{name} must be a CUDA tensor on device {dev_index}")
-            if t.dtype != dtype:
-                raise TypeError(f"{name} must be {dtype}")
-            if tuple(t.shape) != shape:
-                raise TypeError(f"{name} must have shape {shape}, not {tuple(t.shape)}")
-            if not t.is_contiguous():
-                raise TypeError(f"{name} must be contiguous")
-
-        check(init, "init", torch.float64, (B, n, KNOT))
-        check(desired_batch, "desired_batch", torch.float64, (B, n, KNOT))
-        check(out_traj, "out_traj", torch.float64, (B, n, KNOT))
-        check(out_cost, "out_cost", torch.float64, (B,))
-        for t, name in ((out_status, "out_status"), (out_iters, "out_iters"), (out_n_bwd, "out_n_bwd"),
-                        (out_n_fwd, "out_n_fwd")):
-            check(t, name, torch.int32, (B,))
+        self._device_tensors(((init, "init", (B, n, KNOT)), (desired_batch, "desired_batch", (B, n, KNOT)), (out_traj, "out_traj", (B, n, KNOT)),
+                              (out_cost, "out_cost", (B,))) +
+                             tuple((t, name, (B,), torch.int32) for t, name in ((out_status, "out_status"), (out_iters, "out_iters"),
+                                                                                (out_n_bwd, "out_n_bwd"), (out_n_fwd, "out_n_fwd"))))
         # inputs produced by asynchronous torch work on its current stream: the solver's stream waits for them
         if wait_current_stream:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(init.device))
-            rc = load().qilqr_stream_wait_event(self._h, C.c_void_p(ev.cuda_event))
-            if rc:
-                _raise(rc)
+            self._wait_current_stream(init)
         vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-        rc = load().qilqr_solve_batch_device(self._h, vp(init), vp(desired_batch), C.c_int32(B), C.c_int32(n),
-                                             vp(out_traj), vp(out_cost), vp(out_status), vp(out_iters),
-                                             vp(out_n_bwd), vp(out_n_fwd))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_solve_batch_device(self._h, vp(init), vp(desired_batch), C.c_int32(B), C.c_int32(n),
+                                               vp(out_traj), vp(out_cost), vp(out_status), vp(out_iters),
+                                               vp(out_n_bwd), vp(out_n_fwd)))
 
     # ---- the passes the reference tests individually (ilqr_test.cc:102-190), batched
     def cost_trajectory(self, traj):
         traj = _d(traj)
         B, n = traj.shape[0], traj.shape[1]
         cost = np.zeros(B)
-        rc = load().qilqr_cost_trajectory(self._h, _p(traj), C.c_int32(B), C.c_int32(n), _p(cost))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_cost_trajectory(self._h, _p(traj), C.c_int32(B), C.c_int32(n), _p(cost)))
         return cost
 
     def backwards_pass(self, traj):
@@ -454,9 +437,7 @@ class QuadrotorILQRBatch:
         B, n = traj.shape[0], traj.shape[1]
         gains = np.zeros((B, n, GAIN))
         terms = np.zeros((B, 2))
-        rc = load().qilqr_backwards_pass(self._h, _p(traj), C.c_int32(B), C.c_int32(n), _p(gains), _p(terms))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_backwards_pass(self._h, _p(traj), C.c_int32(B), C.c_int32(n), _p(gains), _p(terms)))
         return gains, terms
 
     def forward_sim(self, traj, gains, alpha=1.0):
@@ -464,9 +445,7 @@ class QuadrotorILQRBatch:
         B, n = traj.shape[0], traj.shape[1]
         alpha = _d(np.broadcast_to(alpha, (B,)))
         out = np.zeros_like(traj)
-        rc = load().qilqr_forward_sim(self._h, _p(traj), _p(gains), _p(alpha), C.c_int32(B), C.c_int32(n), _p(out))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_forward_sim(self._h, _p(traj), _p(gains), _p(alpha), C.c_int32(B), C.c_int32(n), _p(out)))
         return out
 
     def line_search(self, traj, cost, gains, terms):
@@ -475,10 +454,8 @@ class QuadrotorILQRBatch:
         out = np.zeros_like(traj)
         oc, step = np.zeros(B), np.zeros(B)
         st = np.zeros(B, dtype=np.int32)
-        rc = load().qilqr_line_search(self._h, _p(traj), _p(cost), _p(gains), _p(terms), C.c_int32(B), C.c_int32(n),
-                                      _p(out), _p(oc), _p(step), _ip(st))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_line_search(self._h, _p(traj), _p(cost), _p(gains), _p(terms), C.c_int32(B), C.c_int32(n),
+                                        _p(out), _p(oc), _p(step), _ip(st)))
         return dict(traj=out, cost=oc, step=step, status=st)
 
     def cost_history(self, B):
@@ -487,95 +464,66 @@ class QuadrotorILQRBatch:
         cap = C.c_int32()
         load().qilqr_cost_history(self._h, C.c_int32(B), None, C.c_int32(0), C.byref(cap))
         hist = np.zeros((B, max(cap.value, 1)))
-        rc = load().qilqr_cost_history(self._h, C.c_int32(B), _p(hist), C.c_int32(hist.shape[1]), C.byref(cap))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_cost_history(self._h, C.c_int32(B), _p(hist), C.c_int32(hist.shape[1]), C.byref(cap)))
         return hist
 
     # ---- profiling
     def profile_reset(self):
-        rc = load().qilqr_profile_reset(self._h)
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_profile_reset(self._h))
 
     def profile_mode(self, mode):
         """0 off, 1 k_backward + k_rollout, 2 every kernel, 3 k_backward only, 4 k_rollout only"""
-        rc = load().qilqr_profile_mode(self._h, C.c_int32(int(mode)))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_profile_mode(self._h, C.c_int32(int(mode))))
 
     def describe(self, B):
         """qilqr_describe: in words, the arithmetic and the kernels a batch solve of B problems on this handle uses"""
         buf = C.create_string_buffer(2048)
-        rc = load().qilqr_describe(self._h, C.c_int32(int(B)), buf, C.c_size_t(len(buf)))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_describe(self._h, C.c_int32(int(B)), buf, C.c_size_t(len(buf))))
         return buf.value.decode()
 
     def compaction_moves(self):
         """trajectories the compaction moved in the last batch solve (qilqr_compaction_moves)"""
         m = C.c_int64()
-        rc = load().qilqr_compaction_moves(self._h, C.byref(m))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_compaction_moves(self._h, C.byref(m)))
         return m.value
 
     def set_regularisation(self, mu_init, mu_factor=10.0, mu_max=1e6):
         """Levenberg-Marquardt restarts (an extension the reference lacks; mu_init = 0 switches it off):
         see qilqr_set_regularisation in include/quadrotor_ilqr.h"""
-        rc = load().qilqr_set_regularisation(self._h, C.c_double(mu_init), C.c_double(mu_factor),
-                                              C.c_double(mu_max))
-        if rc == ERR_INVALID_ARG:
-            raise ValueError(load().qilqr_last_error().decode())
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_regularisation(self._h, C.c_double(mu_init), C.c_double(mu_factor), C.c_double(mu_max)), _raise_regularisation)
 
     def set_integrator(self, integrator):
         """Runge-Kutta extension (the step sketched at quadrotor_model.cc:51-63; 0 = the reference's explicit Euler)."""
-        rc = load().qilqr_set_integrator(self._h, C.c_int32(int(integrator)))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_integrator(self._h, C.c_int32(int(integrator))))
 
     def set_control_limits(self, lo, hi):
         """Per-rotor thrust limits lo <= u_a <= hi (N; scalars or four values, +-inf leaves a side open) -- an extension: box-constrained
         iLQR, see qilqr_set_control_limits in include/quadrotor_ilqr.h.  clear_control_limits() switches it off again."""
         lo = _d(np.broadcast_to(np.asarray(lo, dtype=np.float64), (4,)))
         hi = _d(np.broadcast_to(np.asarray(hi, dtype=np.float64), (4,)))
-        rc = load().qilqr_set_control_limits(self._h, _p(lo), _p(hi))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_control_limits(self._h, _p(lo), _p(hi)))
 
     def clear_control_limits(self):
-        rc = load().qilqr_set_control_limits(self._h, None, None)
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_control_limits(self._h, None, None))
 
     def set_models(self, models):
         """Per-problem models (an extension): problem b of every batch entry point is solved with models[b] -- see model_array for the
         forms `models` takes, and qilqr_set_batch_models in include/quadrotor_ilqr.h.  Every call is then over exactly that many
         problems.  clear_models() switches it off again."""
         arr = model_array(models)
-        rc = load().qilqr_set_batch_models(self._h, C.cast(arr, C.c_void_p), C.c_int32(len(arr)))
-        if rc:
-            _raise_models(rc)
+        _check(load().qilqr_set_batch_models(self._h, C.cast(arr, C.c_void_p), C.c_int32(len(arr))), _raise_models)
 
     def clear_models(self):
-        rc = load().qilqr_set_batch_models(self._h, None, C.c_int32(0))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_batch_models(self._h, None, C.c_int32(0)))
 
     def set_obstacles(self, spheres):
         """Spherical obstacles penalised in the cost (an extension): `spheres` is a (K, 5) array of {cx, cy, cz, radius, weight}, K <= 64,
         shared by every problem -- see qilqr_set_obstacles in include/quadrotor_ilqr.h.  clear_obstacles() switches them off again."""
         arr = obstacle_array(spheres)
-        rc = load().qilqr_set_obstacles(self._h, _p(arr), C.c_int32(len(arr)))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_obstacles(self._h, _p(arr), C.c_int32(len(arr))))
 
     def clear_obstacles(self):
-        rc = load().qilqr_set_obstacles(self._h, None, C.c_int32(0))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_obstacles(self._h, None, C.c_int32(0)))
 
     def set_batch_obstacles(self, spheres, counts=None):
         """Per-problem, moving spheres (an extension): `spheres` is (B, K, 8) {cx, cy, cz, vx, vy, vz, radius, weight} or (B, K, 5) static
@@ -583,36 +531,26 @@ class QuadrotorILQRBatch:
         Every call that evaluates the cost is then over exactly B problems -- see qilqr_set_batch_obstacles in include/quadrotor_ilqr.h.
         clear_batch_obstacles() switches them off again."""
         arr, cnt = batch_obstacle_arrays(spheres, counts)
-        rc = load().qilqr_set_batch_obstacles(self._h, _p(arr), _ip(cnt), C.c_int32(arr.shape[0]), C.c_int32(arr.shape[1]))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_batch_obstacles(self._h, _p(arr), _ip(cnt), C.c_int32(arr.shape[0]), C.c_int32(arr.shape[1])))
 
     def clear_batch_obstacles(self):
-        rc = load().qilqr_set_batch_obstacles(self._h, None, None, C.c_int32(0), C.c_int32(0))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_batch_obstacles(self._h, None, None, C.c_int32(0), C.c_int32(0)))
 
     def set_state_weight_schedule(self, Qs):
         """Per-knot state weights (an extension): `Qs` is an (n, 12, 12) array and knot i of every problem takes Qs[i] for Q -- terminal
         and waypoint costs (problems.terminal_schedule, problems.waypoint_schedule); see qilqr_set_state_weight_schedule in
         include/quadrotor_ilqr.h.  clear_state_weight_schedule() switches it off again."""
         arr = schedule_array(Qs)
-        rc = load().qilqr_set_state_weight_schedule(self._h, _p(arr), C.c_int32(len(arr)))
-        if rc != OK:
-            _raise(rc)
+        _check(load().qilqr_set_state_weight_schedule(self._h, _p(arr), C.c_int32(len(arr))))
 
     def clear_state_weight_schedule(self):
-        rc = load().qilqr_set_state_weight_schedule(self._h, None, C.c_int32(0))
-        if rc != OK:
-            _raise(rc)
+        _check(load().qilqr_set_state_weight_schedule(self._h, None, C.c_int32(0)))
 
     # ---- receding-horizon stepping
     def set_horizon_start(self, k0):
         """From this call on knot i of every call reads desired[k0 + i] of the handle's desired trajectory and Qs[k0 + i] of its
         state-weight schedule (an extension; 0 restores the handle) -- see qilqr_set_horizon_start in include/quadrotor_ilqr.h."""
-        rc = load().qilqr_set_horizon_start(self._h, C.c_int32(int(k0)))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_set_horizon_start(self._h, C.c_int32(int(k0))))
 
     def shift(self, traj, x0=None, steps=1, tail="hold"):
         """qilqr_shift_batch, host arrays: the plan (B, n, 18) moved `steps` knots towards its start, its end extended by dynamics steps
@@ -628,9 +566,7 @@ class QuadrotorILQRBatch:
                 raise TypeError(f"x0 must be ({B}, {STATE}): words 1..13 of a knot per problem")
         out = np.zeros_like(traj)
         vp = lambda a: C.c_void_p(0 if a is None else a.ctypes.data)
-        rc = load().qilqr_shift_batch(self._h, vp(traj), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(int(steps)), C.c_int32(_tail(tail)), vp(out))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_shift_batch(self._h, vp(traj), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(int(steps)), C.c_int32(_tail(tail)), vp(out)))
         return out
 
     def shift_device(self, traj, out, x0=None, steps=1, tail="hold", wait_current_stream=True):
@@ -638,46 +574,30 @@ class QuadrotorILQRBatch:
         or None, on the solver's device, contiguous.  The launch is ENQUEUED on the solver's own stream -- behind whatever torch has
         enqueued on its current stream (wait_current_stream) -- and this returns without waiting: a solve on this handle is ordered behind
         it; torch work that reads `out` waits for the solver's stream first (any draining call of the handle, or an event)."""
-        import torch
         if traj.dim() != 3 or traj.shape[2] != KNOT:
             raise TypeError("traj must be (B, n, 18)")
         B, n = int(traj.shape[0]), int(traj.shape[1])
-        dev_index = load().qilqr_device(self._h)
-        for t, name, shape in ((traj, "traj", (B, n, KNOT)), (out, "out", (B, n, KNOT)), (x0, "x0", (B, STATE))):
-            if t is None and name == "x0":
-                continue
-            if t is None or not t.is_cuda or t.device.index != dev_index:
-                raise TypeError(f"{name} must be a CUDA tensor on device {dev_index}")
-            if t.dtype != torch.float64:
-                raise TypeError(f"{name} must be {torch.float64}")
-            if tuple(t.shape) != shape:
-                raise TypeError(f"{name} must have shape {shape}, not {tuple(t.shape)}")
-            if not t.is_contiguous():
-                raise TypeError(f"{name} must be contiguous")
+        self._device_tensors(((traj, "traj", (B, n, KNOT)), (out, "out", (B, n, KNOT)), (x0, "x0", (B, STATE))), required=("traj", "out"))
         tail = _tail(tail)
         if wait_current_stream:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(traj.device))
-            rc = load().qilqr_stream_wait_event(self._h, C.c_void_p(ev.cuda_event))
-            if rc:
-                _raise(rc)
+            self._wait_current_stream(traj)
         vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-        rc = load().qilqr_shift_batch_device(self._h, vp(traj), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(int(steps)), C.c_int32(tail), vp(out))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_shift_batch_device(self._h, vp(traj), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(int(steps)), C.c_int32(tail), vp(out)))
 
     # ---- the plan's feedback law: gains about a plan on the device, and the law flown from given states
-    def _device_tensors(self, specs):
-        """checks of the device entry points: (tensor, name, shape) float64, contiguous, on the solver's device; None is skipped"""
+    def _device_tensors(self, specs, required=()):
+        """checks of the device entry points: (tensor, name, shape[, dtype]) of that dtype (float64), contiguous, on the solver's device;
+        None is skipped unless the name is in `required`"""
         import torch
         dev_index = load().qilqr_device(self._h)
-        for t, name, shape in specs:
-            if t is None:
+        for t, name, shape, *dtype in specs:
+            dtype = dtype[0] if dtype else torch.float64
+            if t is None and name not in required:
                 continue
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != dev_index:
                 raise TypeError(f"{name} must be a CUDA tensor on device {dev_index}")
-            if t.dtype != torch.float64:
-                raise TypeError(f"{name} must be {torch.float64}")
+            if t.dtype != dtype:
+                raise TypeError(f"{name} must be {dtype}")
             if tuple(t.shape) != shape:
                 raise TypeError(f"{name} must have shape {shape}, not {tuple(t.shape)}")
             if not t.is_contiguous():
@@ -687,9 +607,7 @@ class QuadrotorILQRBatch:
         import torch
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(t.device))
-        rc = load().qilqr_stream_wait_event(self._h, C.c_void_p(ev.cuda_event))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_stream_wait_event(self._h, C.c_void_p(ev.cuda_event)))
 
     def backwards_pass_device(self, traj, gains, terms=None, wait_current_stream=True):
         """qilqr_backwards_pass_device on torch tensors: traj float64 (B, n, 18) -> gains (B, n, 52) and, when given, terms (B, 2), the bits
@@ -704,9 +622,7 @@ class QuadrotorILQRBatch:
         if wait_current_stream:
             self._wait_current_stream(traj)
         vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-        rc = load().qilqr_backwards_pass_device(self._h, vp(traj), C.c_int32(B), C.c_int32(n), vp(gains), vp(terms))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_backwards_pass_device(self._h, vp(traj), C.c_int32(B), C.c_int32(n), vp(gains), vp(terms)))
 
     def closed_loop(self, plan, gains, x0, i0=0, i1=None, traj=True, stats=True, wrench=None, desired=None, score=False):
         """qilqr_closed_loop, host arrays: the law u = u_i + K_i (x (-) plan_i) of plan (B, n, 18) and gains (B, n, 52) flown from the
@@ -714,7 +630,7 @@ class QuadrotorILQRBatch:
         per-problem models (B * S of them: model b S + j flies sample (b, j)).  Returns a dict: traj (B, S, n, 18), NaN outside knots
         i0 .. i1 (traj=True), and stats (B, S, 4): max position error, max rotation error, |dx| at knot i1, clamped (knot, rotor) pairs
         (stats=True).
-        wrench, desired, score (qilqr_closed_loop_scored; without any of them the call is qilqr_closed_loop): wrench (B, S, n_w, 6) -- or
+        wrench, desired, score (without any of them the scored entry point, which is always the one called, is qilqr_closed_loop): wrench (B, S, n_w, 6) -- or
         (B, S, 6): n_w = 1 -- with n_w 1 or n, {F world frame, tau body frame} held over each step; score=True adds score (B, S, 4): the
         handle's cost of the flown knots i0 .. i1, the smallest clearance to any sphere of the handle's two tables, its knot, and the
         number of knots in collision; desired (B, n, 18): the cost is taken against it instead of the handle's desired trajectory."""
@@ -733,12 +649,6 @@ class QuadrotorILQRBatch:
         out_traj = _d16(np.full((B, S, n, KNOT), np.nan)) if traj else None
         out_stats = _d16(np.zeros((B, S, CL_STATS))) if stats else None
         vp = lambda a: C.c_void_p(0 if a is None else a.ctypes.data)
-        if wrench is None and desired is None and not score:
-            rc = load().qilqr_closed_loop(self._h, vp(plan), vp(gains), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1),
-                                          vp(out_traj), vp(out_stats))
-            if rc:
-                _raise(rc)
-            return {k: v for k, v in (("traj", out_traj), ("stats", out_stats)) if v is not None}
         n_w = 1
         if wrench is not None:
             wrench = _d16(wrench)
@@ -752,10 +662,8 @@ class QuadrotorILQRBatch:
             if desired.shape != (B, n, KNOT):
                 raise TypeError(f"desired must be ({B}, {n}, {KNOT}): one desired trajectory per plan")
         out_score = _d16(np.zeros((B, S, CL_SCORE))) if score else None
-        rc = load().qilqr_closed_loop_scored(self._h, vp(plan), vp(gains), vp(x0), vp(wrench), C.c_int32(n_w), vp(desired), C.c_int32(B), C.c_int32(n),
-                                             C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1), vp(out_traj), vp(out_stats), vp(out_score))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_closed_loop_scored(self._h, vp(plan), vp(gains), vp(x0), vp(wrench), C.c_int32(n_w), vp(desired), C.c_int32(B), C.c_int32(n),
+                                               C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1), vp(out_traj), vp(out_stats), vp(out_score)))
         return {k: v for k, v in (("traj", out_traj), ("stats", out_stats), ("score", out_score)) if v is not None}
 
     def closed_loop_device(self, plan, gains, x0, out_traj=None, out_stats=None, i0=0, i1=None, wait_current_stream=True, wrench=None, desired=None,
@@ -764,8 +672,8 @@ class QuadrotorILQRBatch:
         (B, S, n, 18) or None, out_stats (B, S, 4) or None, float64, contiguous, on the solver's device.  Only knots i0 .. i1 of out_traj
         are written.  ENQUEUED on the solver's own stream -- behind whatever torch has enqueued on its current stream
         (wait_current_stream) -- and not waited for: stream ordering as for shift_device.
-        wrench (B, S, n_w, 6), desired (B, n, 18) and out_score (B, S, 4), checked like the others, make the call
-        qilqr_closed_loop_scored_device (closed_loop's docstring); without any of them it is qilqr_closed_loop_device."""
+        wrench (B, S, n_w, 6), desired (B, n, 18) and out_score (B, S, 4), checked like the others, are qilqr_closed_loop_scored_device's
+        (closed_loop's docstring); without any of them that entry point, always the one called, is qilqr_closed_loop_device."""
         if plan is None or plan.dim() != 3 or plan.shape[2] != KNOT:
             raise TypeError("plan must be (B, n, 18)")
         B, n = int(plan.shape[0]), int(plan.shape[1])
@@ -786,15 +694,9 @@ class QuadrotorILQRBatch:
         if wait_current_stream:
             self._wait_current_stream(plan)
         vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-        if wrench is None and desired is None and out_score is None:
-            rc = load().qilqr_closed_loop_device(self._h, vp(plan), vp(gains), vp(x0), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)),
-                                                 C.c_int32(i1), vp(out_traj), vp(out_stats))
-        else:
-            rc = load().qilqr_closed_loop_scored_device(self._h, vp(plan), vp(gains), vp(x0), vp(wrench), C.c_int32(n_w), vp(desired), C.c_int32(B),
-                                                        C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1), vp(out_traj), vp(out_stats),
-                                                        vp(out_score))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_closed_loop_scored_device(self._h, vp(plan), vp(gains), vp(x0), vp(wrench), C.c_int32(n_w), vp(desired), C.c_int32(B),
+                                                      C.c_int32(n), C.c_int32(S), C.c_int32(int(i0)), C.c_int32(i1), vp(out_traj), vp(out_stats),
+                                                      vp(out_score)))
 
     # ---- the ends of the Monte-Carlo loop: gusts and start states sampled, and scores reduced, on the device
     def sample_gusts_device(self, out, seed, sigma, mean=None, tau_force_s=0.0, tau_torque_s=0.0, b0=0, s0=0, wait_current_stream=True):
@@ -809,10 +711,8 @@ class QuadrotorILQRBatch:
         m = gust_model(sigma, mean, tau_force_s, tau_torque_s)
         if wait_current_stream:
             self._wait_current_stream(out)
-        rc = load().qilqr_sample_gusts_device(self._h, C.byref(m), C.c_uint64(int(seed)), C.c_int32(B), C.c_int32(S), C.c_int32(n_w), C.c_int32(int(b0)),
-                                              C.c_int32(int(s0)), C.c_void_p(out.data_ptr()))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_sample_gusts_device(self._h, C.byref(m), C.c_uint64(int(seed)), C.c_int32(B), C.c_int32(S), C.c_int32(n_w), C.c_int32(int(b0)),
+                                                C.c_int32(int(s0)), C.c_void_p(out.data_ptr())))
 
     def sample_states_device(self, x_nom, out, seed, sigma, b0=0, s0=0, first_is_nominal=False, wait_current_stream=True):
         """qilqr_sample_states_device: out[b, s] = x_nom[b] (+) sigma * xi, x_nom (B, 13) and out (B, S, 13) float64 tensors on the solver's
@@ -830,11 +730,9 @@ class QuadrotorILQRBatch:
             raise TypeError("sigma must have 1 or 12 words")
         if wait_current_stream:
             self._wait_current_stream(out)
-        rc = load().qilqr_sample_states_device(self._h, C.c_void_p(x_nom.data_ptr()), C.c_void_p(sig.ctypes.data), C.c_uint64(int(seed)), C.c_int32(B),
-                                               C.c_int32(S), C.c_int32(int(b0)), C.c_int32(int(s0)), C.c_uint32(1 if first_is_nominal else 0),
-                                               C.c_void_p(out.data_ptr()))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_sample_states_device(self._h, C.c_void_p(x_nom.data_ptr()), C.c_void_p(sig.ctypes.data), C.c_uint64(int(seed)), C.c_int32(B),
+                                                 C.c_int32(S), C.c_int32(int(b0)), C.c_int32(int(s0)), C.c_uint32(1 if first_is_nominal else 0),
+                                                 C.c_void_p(out.data_ptr())))
 
     def reduce_scores_device(self, score, out, wait_current_stream=True):
         """qilqr_reduce_scores_device: out (B, 8) from score (B, S, 4) as closed_loop_device's out_score holds it: mean cost, its deviation,
@@ -848,15 +746,11 @@ class QuadrotorILQRBatch:
             raise TypeError(f"out must be a ({B}, {MC_SUMMARY}) tensor")
         if wait_current_stream:
             self._wait_current_stream(score)
-        rc = load().qilqr_reduce_scores_device(self._h, C.c_void_p(score.data_ptr()), C.c_int32(B), C.c_int32(S), C.c_void_p(out.data_ptr()))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_reduce_scores_device(self._h, C.c_void_p(score.data_ptr()), C.c_int32(B), C.c_int32(S), C.c_void_p(out.data_ptr())))
 
     def profile_get(self):
         p = Profile()
-        rc = load().qilqr_profile_get(self._h, C.byref(p))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_profile_get(self._h, C.byref(p)))
         return {f: getattr(p, f) for f, _ in Profile._fields_}
 
 
@@ -879,7 +773,7 @@ class QuadrotorILQRSharded:
                                             C.byref(o), C.byref(dc), C.c_size_t(C.sizeof(dc)), arr, C.c_int32(len(self.devices)), C.byref(self._h))
         if rc:
             self._h = None
-            _raise(rc)
+        _check(rc)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -897,9 +791,7 @@ class QuadrotorILQRSharded:
         out = []
         for r in range(len(self.devices)):
             b0, cnt = C.c_int32(), C.c_int32()
-            rc = load().qilqr_shard_range(C.c_int32(B), C.c_int32(len(self.devices)), C.c_int32(r), C.byref(b0), C.byref(cnt))
-            if rc:
-                _raise(rc)
+            _check(load().qilqr_shard_range(C.c_int32(B), C.c_int32(len(self.devices)), C.c_int32(r), C.byref(b0), C.byref(cnt)))
             out.append((b0.value, cnt.value))
         return out
 
@@ -908,10 +800,8 @@ class QuadrotorILQRSharded:
         B, n = init.shape[0], init.shape[1]
         des = None if desired_batch is None else _d(desired_batch)
         out = _batch_outputs(init, out)
-        rc = load().qilqr_solve_batch_sharded(self._h, _p(init), _p(des), C.c_int32(B), C.c_int32(n), _p(out["traj"]), _p(out["cost"]),
-                                              _ip(out["status"]), _ip(out["iters"]), _ip(out["n_bwd"]), _ip(out["n_fwd"]))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_solve_batch_sharded(self._h, _p(init), _p(des), C.c_int32(B), C.c_int32(n), _p(out["traj"]), _p(out["cost"]),
+                                                _ip(out["status"]), _ip(out["iters"]), _ip(out["n_bwd"]), _ip(out["n_fwd"])))
         return out
 
 
@@ -920,77 +810,53 @@ class QuadrotorILQRSharded:
         lo = _d(np.broadcast_to(np.asarray(lo, dtype=np.float64), (4,)))
         hi = _d(np.broadcast_to(np.asarray(hi, dtype=np.float64), (4,)))
         for r in range(len(self.devices)):
-            rc = load().qilqr_set_control_limits(load().qilqr_sharded_solver(self._h, C.c_int32(r)), _p(lo), _p(hi))
-            if rc:
-                _raise(rc)
+            _check(load().qilqr_set_control_limits(load().qilqr_sharded_solver(self._h, C.c_int32(r)), _p(lo), _p(hi)))
 
     def set_models(self, models):
         """QuadrotorILQRBatch.set_models for the sharded batch: each shard's solver gets its slice (qilqr_sharded_set_batch_models)"""
         arr = model_array(models)
-        rc = load().qilqr_sharded_set_batch_models(self._h, C.cast(arr, C.c_void_p), C.c_int32(len(arr)))
-        if rc:
-            _raise_models(rc)
+        _check(load().qilqr_sharded_set_batch_models(self._h, C.cast(arr, C.c_void_p), C.c_int32(len(arr))), _raise_models)
 
     def clear_models(self):
-        rc = load().qilqr_sharded_set_batch_models(self._h, None, C.c_int32(0))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_sharded_set_batch_models(self._h, None, C.c_int32(0)))
 
     def set_obstacles(self, spheres):
         """QuadrotorILQRBatch.set_obstacles on every shard's solver (qilqr_sharded_set_obstacles)"""
         arr = obstacle_array(spheres)
-        rc = load().qilqr_sharded_set_obstacles(self._h, _p(arr), C.c_int32(len(arr)))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_sharded_set_obstacles(self._h, _p(arr), C.c_int32(len(arr))))
 
     def clear_obstacles(self):
-        rc = load().qilqr_sharded_set_obstacles(self._h, None, C.c_int32(0))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_sharded_set_obstacles(self._h, None, C.c_int32(0)))
 
     def set_batch_obstacles(self, spheres, counts=None):
         """QuadrotorILQRBatch.set_batch_obstacles for the sharded batch: each shard's solver gets its rows (qilqr_sharded_set_batch_obstacles)"""
         arr, cnt = batch_obstacle_arrays(spheres, counts)
-        rc = load().qilqr_sharded_set_batch_obstacles(self._h, _p(arr), _ip(cnt), C.c_int32(arr.shape[0]), C.c_int32(arr.shape[1]))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_sharded_set_batch_obstacles(self._h, _p(arr), _ip(cnt), C.c_int32(arr.shape[0]), C.c_int32(arr.shape[1])))
 
     def clear_batch_obstacles(self):
-        rc = load().qilqr_sharded_set_batch_obstacles(self._h, None, None, C.c_int32(0), C.c_int32(0))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_sharded_set_batch_obstacles(self._h, None, None, C.c_int32(0), C.c_int32(0)))
 
     def set_state_weight_schedule(self, Qs):
         """QuadrotorILQRBatch.set_state_weight_schedule on every shard's solver (qilqr_sharded_set_state_weight_schedule)"""
         arr = schedule_array(Qs)
-        rc = load().qilqr_sharded_set_state_weight_schedule(self._h, _p(arr), C.c_int32(len(arr)))
-        if rc != OK:
-            _raise(rc)
+        _check(load().qilqr_sharded_set_state_weight_schedule(self._h, _p(arr), C.c_int32(len(arr))))
 
     def clear_state_weight_schedule(self):
-        rc = load().qilqr_sharded_set_state_weight_schedule(self._h, None, C.c_int32(0))
-        if rc != OK:
-            _raise(rc)
+        _check(load().qilqr_sharded_set_state_weight_schedule(self._h, None, C.c_int32(0)))
 
     def set_horizon_start(self, k0):
         """QuadrotorILQRBatch.set_horizon_start on every shard's solver (qilqr_sharded_set_horizon_start: checked once, all or none)"""
-        rc = load().qilqr_sharded_set_horizon_start(self._h, C.c_int32(int(k0)))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_sharded_set_horizon_start(self._h, C.c_int32(int(k0))))
 
     def clear_control_limits(self):
         for r in range(len(self.devices)):
-            rc = load().qilqr_set_control_limits(load().qilqr_sharded_solver(self._h, C.c_int32(r)), None, None)
-            if rc:
-                _raise(rc)
+            _check(load().qilqr_set_control_limits(load().qilqr_sharded_solver(self._h, C.c_int32(r)), None, None))
 
     TRANSPORTS = {"auto": 0, "rccl": 1, "peer_copy": 2}
 
     def set_transport(self, transport):
         """how qilqr_solve_batch_sharded_device moves the shards' rows to the root: 'auto', 'rccl' (ncclSend / ncclRecv), 'peer_copy'"""
-        rc = load().qilqr_sharded_set_transport(self._h, C.c_int32(self.TRANSPORTS[transport]))
-        if rc:
-            _raise(rc)
+        _check(load().qilqr_sharded_set_transport(self._h, C.c_int32(self.TRANSPORTS[transport])))
         return self.transport()
 
     def transport(self):
@@ -1015,12 +881,10 @@ class QuadrotorILQRSharded:
             return C.c_void_p(t.data_ptr())
 
         ms = C.c_double(0.0)
-        rc = load().qilqr_solve_batch_sharded_device(
+        _check(load().qilqr_solve_batch_sharded_device(
             self._h, _p(init), _p(des), C.c_int32(B), C.c_int32(n), C.c_int32(root), ptr(out_traj, "torch.float64", (B, n, 18)),
             ptr(out_cost, "torch.float64", (B,)), ptr(out_status, "torch.int32", (B,)), ptr(out_iters, "torch.int32", (B,)),
-            ptr(out_n_bwd, "torch.int32", (B,)), ptr(out_n_fwd, "torch.int32", (B,)), C.byref(ms))
-        if rc:
-            _raise(rc)
+            ptr(out_n_bwd, "torch.int32", (B,)), ptr(out_n_fwd, "torch.int32", (B,)), C.byref(ms)))
         return ms.value
 
 

@@ -1,39 +1,30 @@
 // closed_loop_scored.hip -- the translation unit of k_closed_loop_scored (closed_loop_scored_kernels.h), the device side of
 // qilqr_closed_loop_scored[_device].  A unit beside closed_loop.hip, whose sixteen kernels stay what they were: the 48 instantiations here
 // are {wrench, score, both} x k_closed_loop's sixteen.  Exports one hidden function, launch_closed_loop_scored (closed_loop_launch.h), which
-// host/api_calls.h calls; the rule of the forms is closed_loop_shared_form, and the diagnostics build's switch of it is closed_loop.hip's.
+// host/caller_arrays.h calls; the form and the grid are closed_loop.hip's closed_loop_form.
 #include <hip/hip_runtime.h>
 
 #include "closed_loop_scored_kernels.h"
 #include "closed_loop_launch.h"
-
-#ifdef QILQR_DIAG
-extern "C" int qilqr_debug_closed_loop_form(void);
-#endif
+#include "launch_ext.h"
 
 namespace qilqr {
 
 namespace {
-template <int INTEG, bool SHARED, bool WRENCH, bool SCORE, typename... Lim>
-hipError_t scored_go(hipStream_t stream, const ModelConsts<double> &c, const ClosedLoopArgs &a, const ClosedLoopScoreArgs &e, dim3 grid, Lim... lim) {
-  hipLaunchKernelGGL((k_closed_loop_scored<INTEG, SHARED, WRENCH, SCORE, Lim...>), grid, dim3(CL_BLOCK), 0, stream, c, a, e, lim...);
-  return hipGetLastError();
-}
 template <int INTEG, bool SHARED, bool WRENCH, bool SCORE>
-hipError_t scored_ext(hipStream_t stream, const ModelConsts<double> &c, const ClosedLoopArgs &a, const ClosedLoopScoreArgs &e, dim3 grid,
-                      const ClosedLoopLaunch &call) {
-  const BatchModels bm{call.d_models};
-  if (call.limits && call.d_models) return scored_go<INTEG, SHARED, WRENCH, SCORE>(stream, c, a, e, grid, *call.limits, bm);
-  if (call.limits) return scored_go<INTEG, SHARED, WRENCH, SCORE>(stream, c, a, e, grid, *call.limits);
-  if (call.d_models) return scored_go<INTEG, SHARED, WRENCH, SCORE>(stream, c, a, e, grid, bm);
-  return scored_go<INTEG, SHARED, WRENCH, SCORE>(stream, c, a, e, grid);
+hipError_t scored_go(hipStream_t stream, const ModelConsts<double> &c, const ClosedLoopArgs &a, const ClosedLoopScoreArgs &e, dim3 grid,
+                     const ClosedLoopLaunch &call) {
+  return with_extensions(call.limits, call.d_models, [&](auto... lim) {
+    hipLaunchKernelGGL((k_closed_loop_scored<INTEG, SHARED, WRENCH, SCORE, decltype(lim)...>), grid, dim3(CL_BLOCK), 0, stream, c, a, e, lim...);
+    return hipGetLastError();
+  });
 }
 template <int INTEG, bool SHARED>
 hipError_t scored_switch(hipStream_t stream, const ModelConsts<double> &c, const ClosedLoopArgs &a, const ClosedLoopScoreArgs &e, dim3 grid,
                          const ClosedLoopLaunch &call) {
-  if (e.wrench && e.out_score) return scored_ext<INTEG, SHARED, true, true>(stream, c, a, e, grid, call);
-  if (e.wrench) return scored_ext<INTEG, SHARED, true, false>(stream, c, a, e, grid, call);
-  return scored_ext<INTEG, SHARED, false, true>(stream, c, a, e, grid, call);
+  if (e.wrench && e.out_score) return scored_go<INTEG, SHARED, true, true>(stream, c, a, e, grid, call);
+  if (e.wrench) return scored_go<INTEG, SHARED, true, false>(stream, c, a, e, grid, call);
+  return scored_go<INTEG, SHARED, false, true>(stream, c, a, e, grid, call);
 }
 }  // namespace
 
@@ -42,14 +33,9 @@ hipError_t launch_closed_loop_scored(hipStream_t stream, const ModelConsts<doubl
   if (!s.d_wrench && !s.d_out_score) return launch_closed_loop(stream, consts, call);  // the existing instantiations: the parent's bits
   const ClosedLoopArgs a{call.d_plan, call.d_gains, call.d_x0, call.d_out_traj, call.d_out_stats, call.B, call.n, call.S, call.i0, call.i1};
   const ClosedLoopScoreArgs e{s.d_wrench, s.n_w, s.d_desired, s.desired_step, s.d_q, s.q_step, s.d_shared, s.n_shared, s.d_own, s.d_own_counts, s.own_K, s.d_out_score};
-  bool shared = closed_loop_shared_form(call.S);
-#ifdef QILQR_DIAG
-  if (qilqr_debug_closed_loop_form() >= 0) shared = qilqr_debug_closed_loop_form() != 0;
-#endif
-  const long per = (call.S + CL_BLOCK - 1) / CL_BLOCK;
-  const long blocks = shared ? (long)call.B * per : ((long)call.B * call.S + CL_BLOCK - 1) / CL_BLOCK;
-  if (blocks > 0x7fffffffl) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)blocks);
+  bool shared;
+  dim3 grid;
+  if (!closed_loop_form(call.B, call.S, &shared, &grid)) return hipErrorInvalidValue;
   if (shared) return call.integrator == 1 ? scored_switch<1, true>(stream, consts, a, e, grid, call) : scored_switch<0, true>(stream, consts, a, e, grid, call);
   return call.integrator == 1 ? scored_switch<1, false>(stream, consts, a, e, grid, call) : scored_switch<0, false>(stream, consts, a, e, grid, call);
 }

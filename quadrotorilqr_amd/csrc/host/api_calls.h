@@ -1,6 +1,6 @@
-// host/api_calls.h -- the C ABI of the computing calls on one handle: the batch solves, qilqr_solve, the four stand-alone passes, the
-// pinned host memory for their callers, the receding-horizon shift (whose kernel is shift.hip's), the backward pass over device arrays and the
-// closed-loop flights of a plan (whose kernel is closed_loop.hip's).  Part of ilqr_capi.hip's translation unit.
+// host/api_calls.h -- the C ABI of the computing calls on one handle's workspace: the batch solves, qilqr_solve, the four stand-alone passes
+// and the pinned host memory for their callers.  (The calls on the caller's own arrays are host/caller_arrays.h's.)  Part of ilqr_capi.hip's
+// translation unit.
 #pragma once
 
 extern "C" {
@@ -251,16 +251,10 @@ int qilqr_line_search(qilqr_solver *s, const double *traj, const double *cost, c
   if (!s || !traj || !cost || !gains || !terms) return fail(QILQR_ERR_INVALID_ARG, "null argument");
   int rc = begin_batch(s, B, n, nullptr, E_PASS);
   if (rc) return rc;
-  struct Scratch {  // freed on every return path
-    double *cost = nullptr, *terms = nullptr;
-    ~Scratch() {
-      if (cost) (void)hipFree(cost);
-      if (terms) (void)hipFree(terms);
-    }
-  } scratch;
-  HIP_TRY(hipMalloc((void **)&scratch.cost, sizeof(double) * B));
-  HIP_TRY(hipMalloc((void **)&scratch.terms, sizeof(double) * 2 * B));
-  double *const d_cost = scratch.cost, *const d_terms = scratch.terms;
+  DeviceScratch scratch_cost, scratch_terms;
+  HIP_TRY(hipMalloc((void **)&scratch_cost.p, sizeof(double) * B));
+  HIP_TRY(hipMalloc((void **)&scratch_terms.p, sizeof(double) * 2 * B));
+  double *const d_cost = scratch_cost.p, *const d_terms = scratch_terms.p;
   if ((rc = upload_tiled(s, traj, s->st.traj[0], B, n, 18))) return rc;
   if ((rc = upload_tiled(s, gains, s->st.gains, B, n, 52))) return rc;
   HIP_TRY(hipMemcpyAsync(d_cost, cost, sizeof(double) * B, hipMemcpyHostToDevice, s->stream));
@@ -292,327 +286,5 @@ int qilqr_line_search(qilqr_solver *s, const double *traj, const double *cost, c
   if (out_traj && (rc = download_tiled(s, out_traj, s->st.traj[0], s->st.traj[1], s->st.cur, 0, B, n, 18))) return rc;
   HIP_TRY(hipGetLastError());
   return device_error(s);
-}
-
-// ---- the step between two solves of a receding horizon: k_shift (shift_kernels.h, compiled by shift.hip) on the caller's arrays
-namespace {
-// what both forms refuse (the pointers are the caller's: host ones for qilqr_shift_batch, device ones for qilqr_shift_batch_device)
-int shift_refuse(const qilqr_solver *s, const double *traj, const double *x0, int32_t B, int32_t n, int32_t steps, int32_t tail,
-                 const double *out) {
-  if (!s || !traj || !out) return fail(QILQR_ERR_INVALID_ARG, "null argument");
-  if (B <= 0 || n <= 0) return fail(QILQR_ERR_INVALID_ARG, "B and n must be positive");
-  if (steps < 0 || steps > n - 1)
-    return fail(QILQR_ERR_INVALID_ARG, "shift: steps must be 0 ... n - 1 (" + std::to_string(steps) + " with n = " + std::to_string(n) + ")");
-  if (tail != QILQR_TAIL_HOLD && tail != QILQR_TAIL_HOVER) return fail(QILQR_ERR_INVALID_ARG, "shift: tail must be QILQR_TAIL_HOLD or QILQR_TAIL_HOVER");
-  if (s->f32) return fail(QILQR_ERR_INVALID_ARG, "shift: needs precision 0 (fp64)");
-  if (s->modeled && B != s->models_B)
-    return fail(QILQR_ERR_INVALID_ARG, "batch models were set for B = " + std::to_string(s->models_B) + " problems; this shift has B = " +
-                                           std::to_string(B) + " (set them again, or clear them, for another batch)");
-  if (((uintptr_t)traj | (uintptr_t)out | (uintptr_t)x0) & 15) return fail(QILQR_ERR_INVALID_ARG, "shift: every array must be 16-byte aligned");
-  // the copy is parallel and every block reads only the input: an output that overlaps an input is a race
-  const char *i0 = (const char *)traj, *o0 = (const char *)out, *x = (const char *)x0;
-  const size_t tb = sizeof(double) * 18 * (size_t)B * n, xb = sizeof(double) * QILQR_STATE * (size_t)B;
-  if (i0 < o0 + tb && o0 < i0 + tb) return fail(QILQR_ERR_INVALID_ARG, "shift: the output overlaps the input (the shift does not work in place)");
-  if (x && x < o0 + tb && o0 < x + xb) return fail(QILQR_ERR_INVALID_ARG, "shift: the output overlaps x0");
-  return QILQR_OK;
-}
-int shift_enqueue(qilqr_solver *s, const double *d_traj, const double *d_x0, int32_t B, int32_t n, int32_t steps, int32_t tail, double *d_out) {
-  const ShiftLaunch call{d_traj, d_x0, d_out, B, n, steps, tail, s->integrator, s->limited ? &s->limits : nullptr, s->modeled ? s->d_models : nullptr};
-  const hipError_t e = launch_shift(s->stream, s->consts, call);
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_shift: ") + hipGetErrorString(e));
-  return QILQR_OK;
-}
-}  // namespace
-
-static_assert(QILQR_STATE == 13 && QILQR_TAIL_HOLD == 0 && QILQR_TAIL_HOVER == 1, "shift_kernels.h and the C header agree on the state words and the tails");
-int qilqr_shift_batch_device(qilqr_solver *s, const double *d_traj, const double *d_x0, int32_t B, int32_t n, int32_t steps, int32_t tail,
-                             double *d_out) {
-  int rc = shift_refuse(s, d_traj, d_x0, B, n, steps, tail, d_out);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return shift_enqueue(s, d_traj, d_x0, B, n, steps, tail, d_out);  // (enqueued on the handle's stream; not waited for)
-}
-
-int qilqr_shift_batch(qilqr_solver *s, const double *traj, const double *x0, int32_t B, int32_t n, int32_t steps, int32_t tail, double *out) {
-  int rc = shift_refuse(s, traj, x0, B, n, steps, tail, out);
-  if (rc) return rc;
-  if (x0)  // as the initial trajectories are checked (manif's constructor check), naming the problem
-    for (long b = 0; b < B; ++b) {
-      const double *q = x0 + b * QILQR_STATE + 3;
-      const double nn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-      if (!(std::fabs(nn - 1.0) <= 1e-10)) return fail(QILQR_ERR_BAD_QUATERNION, "x0: quaternion not normalized at problem " + std::to_string(b));
-    }
-  HIP_TRY(hipSetDevice(s->device));
-  struct Scratch {  // freed on every return path
-    double *p = nullptr;
-    ~Scratch() {
-      if (p) (void)hipFree(p);
-    }
-  } scratch;
-  const size_t cnt = 18 * (size_t)B * n, xcnt = (size_t)QILQR_STATE * B;  // (cnt is even: input, output and x0 each start on 16 bytes)
-  HIP_TRY(hipMalloc((void **)&scratch.p, sizeof(double) * (2 * cnt + xcnt)));
-  double *d_in = scratch.p, *d_out = d_in + cnt, *d_x0 = x0 ? d_out + cnt : nullptr;
-  HIP_TRY(hipMemcpyAsync(d_in, traj, sizeof(double) * cnt, hipMemcpyHostToDevice, s->stream));
-  if (x0) HIP_TRY(hipMemcpyAsync(d_x0, x0, sizeof(double) * QILQR_STATE * (size_t)B, hipMemcpyHostToDevice, s->stream));
-  hipError_t e = hipSuccess;
-  if ((rc = shift_enqueue(s, d_in, d_x0, B, n, steps, tail, d_out)) == QILQR_OK)
-    e = hipMemcpyAsync(out, d_out, sizeof(double) * cnt, hipMemcpyDeviceToHost, s->stream);
-  const hipError_t drained = hipStreamSynchronize(s->stream);  // (the copies read and write the caller's arrays, the kernel the scratch: finished before either goes)
-  if (rc) return rc;
-  if (e == hipSuccess) e = drained;
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("qilqr_shift_batch: ") + hipGetErrorString(e));
-  return QILQR_OK;
-}
-
-// ---- gains about a plan that already sits on the device: qilqr_backwards_pass over plain device arrays -- the same linearise / k_init /
-// launch_backward sequence through to_tiled / from_tiled, without the io scratch and the two copies over PCIe
-int qilqr_backwards_pass_device(qilqr_solver *s, const double *d_traj, int32_t B, int32_t n, double *d_gains, double *d_terms) {
-  if (!s || !d_traj || !d_gains) return fail(QILQR_ERR_INVALID_ARG, "null argument");
-  int rc = begin_batch(s, B, n, nullptr, E_PASS);
-  if (rc) return rc;
-  if ((rc = to_tiled(s, d_traj, s->st.traj[0], B, n, 18))) return rc;
-  if ((rc = launch_linearize(s, B, n, 0, 0))) return rc;
-  launch(s, K_OTHER, k_init, dim3(cdiv(B, 64)), dim3(64), s->params, s->st, (int)B, (int)n);
-  if ((rc = launch_backward(s, B, n, 1))) return rc;
-  if ((rc = from_tiled(s, d_gains, s->st.gains, s->st.gains, nullptr, 0, B, n, 52))) return rc;
-  if (d_terms) HIP_TRY(hipMemcpyAsync(d_terms, s->st.terms, sizeof(double) * 2 * B, hipMemcpyDeviceToDevice, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipGetLastError());
-  return device_error(s);
-}
-
-// ---- the plan's feedback law flown from given states: k_closed_loop (closed_loop_kernels.h, compiled by closed_loop.hip) on the caller's arrays
-namespace {
-// what both forms refuse (closed_loop_launch.h: the rule, from facts alone; the pointers are the caller's, host or device ones)
-int closed_loop_refuse(const qilqr_solver *s, const double *plan, const double *gains, const double *x0, int32_t B, int32_t n, int32_t S,
-                       int32_t i0, int32_t i1, const double *out_traj, const double *out_stats) {
-  const ClosedLoopCall call{plan, gains, x0, out_traj, out_stats, B, n, S, i0, i1, s != nullptr, s && s->f32, s && s->modeled, s ? s->models_B : 0};
-  const char *why = closed_loop_refusal(call);
-  if (!why) return QILQR_OK;
-  std::string text = why;
-  if (s && s->modeled && !s->f32 && s->models_B != (long)B * S)
-    text += ": they were set for " + std::to_string(s->models_B) + ", this call has B * S = " + std::to_string((long)B * S);
-  return fail(QILQR_ERR_INVALID_ARG, text);
-}
-int closed_loop_enqueue(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0, int32_t B, int32_t n, int32_t S,
-                        int32_t i0, int32_t i1, double *d_out_traj, double *d_out_stats) {
-  const ClosedLoopLaunch call{d_plan, d_gains, d_x0, d_out_traj, d_out_stats, B, n, S, i0, i1, s->integrator, s->limited ? &s->limits : nullptr,
-                              s->modeled ? s->d_models : nullptr};
-  const hipError_t e = launch_closed_loop(s->stream, s->consts, call);
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_closed_loop: ") + hipGetErrorString(e));
-  return QILQR_OK;
-}
-}  // namespace
-
-static_assert(QILQR_CL_STATS == 4, "closed_loop_kernels.h and the C header agree on the words of a sample's statistics");
-int qilqr_closed_loop_device(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0, int32_t B, int32_t n, int32_t S,
-                             int32_t i0, int32_t i1, double *d_out_traj, double *d_out_stats) {
-  int rc = closed_loop_refuse(s, d_plan, d_gains, d_x0, B, n, S, i0, i1, d_out_traj, d_out_stats);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return closed_loop_enqueue(s, d_plan, d_gains, d_x0, B, n, S, i0, i1, d_out_traj, d_out_stats);  // (enqueued on the handle's stream; not waited for)
-}
-
-int qilqr_closed_loop(qilqr_solver *s, const double *plan, const double *gains, const double *x0, int32_t B, int32_t n, int32_t S, int32_t i0,
-                      int32_t i1, double *out_traj, double *out_stats) {
-  int rc = closed_loop_refuse(s, plan, gains, x0, B, n, S, i0, i1, out_traj, out_stats);
-  if (rc) return rc;
-  for (long r = 0; r < (long)B * S; ++r) {  // as the initial trajectories are checked (manif's constructor check), naming the sample
-    const double *q = x0 + r * QILQR_STATE + 3;
-    const double nn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (!(std::fabs(nn - 1.0) <= 1e-10))
-      return fail(QILQR_ERR_BAD_QUATERNION, "x0: quaternion not normalized at problem " + std::to_string(r / S) + ", sample " + std::to_string(r % S));
-  }
-  HIP_TRY(hipSetDevice(s->device));
-  struct Scratch {  // freed on every return path
-    double *p = nullptr;
-    ~Scratch() {
-      if (p) (void)hipFree(p);
-    }
-  } scratch;
-  // (every count but x0's is even, and x0 goes last: each array starts on 16 bytes)
-  const size_t samples = (size_t)B * S, pc = 18 * (size_t)B * n, gc = 52 * (size_t)B * n, xc = (size_t)QILQR_STATE * samples;
-  const size_t tc = out_traj ? 18 * samples * n : 0, sc = out_stats ? QILQR_CL_STATS * samples : 0;
-  HIP_TRY(hipMalloc((void **)&scratch.p, sizeof(double) * (pc + gc + tc + sc + xc)));
-  double *d_plan = scratch.p, *d_gains = d_plan + pc, *d_traj = d_gains + gc, *d_stats = d_traj + tc, *d_x0 = d_stats + sc;
-  HIP_TRY(hipMemcpyAsync(d_plan, plan, sizeof(double) * pc, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(d_gains, gains, sizeof(double) * gc, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(d_x0, x0, sizeof(double) * xc, hipMemcpyHostToDevice, s->stream));
-  hipError_t e = hipSuccess;
-  if ((rc = closed_loop_enqueue(s, d_plan, d_gains, d_x0, B, n, S, i0, i1, out_traj ? d_traj : nullptr, out_stats ? d_stats : nullptr)) == QILQR_OK) {
-    // knots i0 .. i1 of every sample, and nothing else of the caller's array: rows of (i1 - i0 + 1) knots at a pitch of n knots
-    const size_t pitch = sizeof(double) * 18 * (size_t)n, off = 18 * (size_t)i0;
-    if (out_traj)
-      e = hipMemcpy2DAsync(out_traj + off, pitch, d_traj + off, pitch, sizeof(double) * 18 * (size_t)(i1 - i0 + 1), samples, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess && out_stats) e = hipMemcpyAsync(out_stats, d_stats, sizeof(double) * sc, hipMemcpyDeviceToHost, s->stream);
-  }
-  const hipError_t drained = hipStreamSynchronize(s->stream);  // (the copies read and write the caller's arrays, the kernel the scratch: finished before either goes)
-  if (rc) return rc;
-  if (e == hipSuccess) e = drained;
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("qilqr_closed_loop: ") + hipGetErrorString(e));
-  return QILQR_OK;
-}
-
-// ---- the scored flight: k_closed_loop_scored (closed_loop_scored_kernels.h, compiled by closed_loop_scored.hip) on the caller's arrays
-namespace {
-// what both forms refuse (closed_loop_launch.h: closed_loop_scored_refusal; the pointers are the caller's, host or device ones)
-int closed_loop_scored_refuse(const qilqr_solver *s, const double *plan, const double *gains, const double *x0, const double *wrench, int32_t n_w,
-                              const double *desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1, const double *out_traj,
-                              const double *out_stats, const double *out_score) {
-  const ClosedLoopCall base{plan, gains, x0, out_traj, out_stats, B, n, S, i0, i1, s != nullptr, s && s->f32, s && s->modeled, s ? s->models_B : 0, out_score};
-  const ClosedLoopScoredCall call{base, wrench, desired, n_w, s ? s->pobs_B : 0, s ? s->n_desired : 0, s ? s->n_sched : 0, s ? s->k0 : 0};
-  bool length = false;
-  const char *why = closed_loop_scored_refusal(call, &length);
-  if (!why) return QILQR_OK;
-  std::string text = why;
-  if (length)
-    return fail(QILQR_ERR_LENGTH_MISMATCH, text + " (i1 = " + std::to_string(i1) + ", horizon start " + std::to_string(s->k0) + ", desired trajectory of " +
-                                               std::to_string(s->n_desired) + " knots" + (s->n_sched > 0 ? ", schedule of " + std::to_string(s->n_sched) : std::string()) + ")");
-  if (s && s->modeled && !s->f32 && s->models_B != (long)B * S) text += ": they were set for " + std::to_string(s->models_B) + ", this call has B * S = " + std::to_string((long)B * S);
-  return fail(QILQR_ERR_INVALID_ARG, text);
-}
-int closed_loop_scored_enqueue(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0, const double *d_wrench, int32_t n_w,
-                               const double *d_desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1, double *d_out_traj, double *d_out_stats,
-                               double *d_out_score) {
-  ClosedLoopScoredLaunch call{};
-  call.base = ClosedLoopLaunch{d_plan, d_gains, d_x0, d_out_traj, d_out_stats, B, n, S, i0, i1, s->integrator, s->limited ? &s->limits : nullptr,
-                              s->modeled ? s->d_models : nullptr};
-  call.d_wrench = d_wrench;
-  call.n_w = n_w;
-  call.d_out_score = d_out_score;
-  if (d_out_score) {
-    call.d_desired = d_desired ? d_desired : (const double *)s->d_desired + 18 * (size_t)s->k0;
-    call.desired_step = d_desired ? 18l * n : 0;
-    if (s->n_sched > 0) {
-      call.d_q = s->d_qsched + (size_t)SCHED_WORDS * s->k0;
-      call.q_step = SCHED_WORDS;
-    } else {
-      if (!s->d_cl_q) {  // (Q lies 8 bytes off a 16-byte boundary inside ModelConsts: a copy of its own, made once; the handle's Q never changes)
-        HIP_TRY(hipMalloc((void **)&s->d_cl_q, sizeof(double) * 144));
-        HIP_TRY(hipMemcpyAsync(s->d_cl_q, s->consts.Q, sizeof(double) * 144, hipMemcpyHostToDevice, s->stream));
-      }
-      call.d_q = s->d_cl_q;
-      call.q_step = 0;
-    }
-    call.d_shared = s->n_obstacles > 0 ? s->d_obstacles : nullptr;
-    call.n_shared = s->n_obstacles;
-    call.d_own = s->pobs_B > 0 ? s->d_pobs : nullptr;
-    call.d_own_counts = s->pobs_B > 0 ? s->d_pobs_counts : nullptr;
-    call.own_K = s->pobs_K;
-  }
-  const hipError_t e = launch_closed_loop_scored(s->stream, s->consts, call);
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_closed_loop_scored: ") + hipGetErrorString(e));
-  return QILQR_OK;
-}
-}  // namespace
-
-static_assert(QILQR_CL_SCORE == 4 && QILQR_WRENCH == 6, "closed_loop_kernels.h and the C header agree on the words of a score and of a wrench");
-int qilqr_closed_loop_scored_device(qilqr_solver *s, const double *d_plan, const double *d_gains, const double *d_x0, const double *d_wrench,
-                                    int32_t n_w, const double *d_desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1,
-                                    double *d_out_traj, double *d_out_stats, double *d_out_score) {
-  int rc = closed_loop_scored_refuse(s, d_plan, d_gains, d_x0, d_wrench, n_w, d_desired, B, n, S, i0, i1, d_out_traj, d_out_stats, d_out_score);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return closed_loop_scored_enqueue(s, d_plan, d_gains, d_x0, d_wrench, n_w, d_desired, B, n, S, i0, i1, d_out_traj, d_out_stats, d_out_score);  // (not waited for)
-}
-
-int qilqr_closed_loop_scored(qilqr_solver *s, const double *plan, const double *gains, const double *x0, const double *wrench, int32_t n_w,
-                             const double *desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1, double *out_traj, double *out_stats,
-                             double *out_score) {
-  int rc = closed_loop_scored_refuse(s, plan, gains, x0, wrench, n_w, desired, B, n, S, i0, i1, out_traj, out_stats, out_score);
-  if (rc) return rc;
-  for (long r = 0; r < (long)B * S; ++r) {  // as qilqr_closed_loop checks them
-    const double *q = x0 + r * QILQR_STATE + 3;
-    const double nn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (!(std::fabs(nn - 1.0) <= 1e-10))
-      return fail(QILQR_ERR_BAD_QUATERNION, "x0: quaternion not normalized at problem " + std::to_string(r / S) + ", sample " + std::to_string(r % S));
-  }
-  if (wrench)
-    for (long r = 0; r < (long)B * S; ++r)
-      for (long k = 0; k < n_w; ++k)
-        for (int w = 0; w < QILQR_WRENCH; ++w)
-          if (!std::isfinite(wrench[(r * n_w + k) * QILQR_WRENCH + w]))
-            return fail(QILQR_ERR_INVALID_ARG, "wrench: a non-finite value at problem " + std::to_string(r / S) + ", sample " + std::to_string(r % S) + ", knot " +
-                                                   std::to_string(k));
-  HIP_TRY(hipSetDevice(s->device));
-  struct Scratch {  // freed on every return path
-    double *p = nullptr;
-    ~Scratch() {
-      if (p) (void)hipFree(p);
-    }
-  } scratch;
-  // (every count but x0's is even, and x0 goes last: each array starts on 16 bytes)
-  const size_t samples = (size_t)B * S, pc = 18 * (size_t)B * n, gc = 52 * (size_t)B * n, xc = (size_t)QILQR_STATE * samples;
-  const size_t tc = out_traj ? 18 * samples * n : 0, sc = out_stats ? QILQR_CL_STATS * samples : 0, oc = out_score ? QILQR_CL_SCORE * samples : 0;
-  const size_t wc = wrench ? QILQR_WRENCH * samples * (size_t)n_w : 0, dc = desired ? pc : 0;
-  HIP_TRY(hipMalloc((void **)&scratch.p, sizeof(double) * (pc + gc + tc + sc + oc + wc + dc + xc)));
-  double *d_plan = scratch.p, *d_gains = d_plan + pc, *d_traj = d_gains + gc, *d_stats = d_traj + tc, *d_score = d_stats + sc, *d_wrench = d_score + oc,
-         *d_desired = d_wrench + wc, *d_x0 = d_desired + dc;
-  HIP_TRY(hipMemcpyAsync(d_plan, plan, sizeof(double) * pc, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(d_gains, gains, sizeof(double) * gc, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(d_x0, x0, sizeof(double) * xc, hipMemcpyHostToDevice, s->stream));
-  if (wrench) HIP_TRY(hipMemcpyAsync(d_wrench, wrench, sizeof(double) * wc, hipMemcpyHostToDevice, s->stream));
-  if (desired) HIP_TRY(hipMemcpyAsync(d_desired, desired, sizeof(double) * dc, hipMemcpyHostToDevice, s->stream));
-  hipError_t e = hipSuccess;
-  if ((rc = closed_loop_scored_enqueue(s, d_plan, d_gains, d_x0, wrench ? d_wrench : nullptr, n_w, desired ? d_desired : nullptr, B, n, S, i0, i1,
-                                       out_traj ? d_traj : nullptr, out_stats ? d_stats : nullptr, out_score ? d_score : nullptr)) == QILQR_OK) {
-    const size_t pitch = sizeof(double) * 18 * (size_t)n, off = 18 * (size_t)i0;
-    if (out_traj)
-      e = hipMemcpy2DAsync(out_traj + off, pitch, d_traj + off, pitch, sizeof(double) * 18 * (size_t)(i1 - i0 + 1), samples, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess && out_stats) e = hipMemcpyAsync(out_stats, d_stats, sizeof(double) * sc, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess && out_score) e = hipMemcpyAsync(out_score, d_score, sizeof(double) * oc, hipMemcpyDeviceToHost, s->stream);
-  }
-  const hipError_t drained = hipStreamSynchronize(s->stream);  // (the copies read and write the caller's arrays, the kernel the scratch: finished before either goes)
-  if (rc) return rc;
-  if (e == hipSuccess) e = drained;
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("qilqr_closed_loop_scored: ") + hipGetErrorString(e));
-  return QILQR_OK;
-}
-
-// ---- the ends of the Monte-Carlo loop: k_sample_gusts, k_sample_states and k_reduce_scores (monte_carlo_kernels.h, compiled by
-// monte_carlo.hip) on the caller's device arrays.  The handle gives its stream, its device and its dt; the rules are monte_carlo_launch.h's.
-static_assert(QILQR_MC_SUMMARY == 8, "monte_carlo_kernels.h and the C header agree on the words of a plan's summary");
-int qilqr_sample_gusts_device(qilqr_solver *s, const qilqr_gust_model *m, uint64_t seed, int32_t B, int32_t S, int32_t n_w, int32_t b0, int32_t s0,
-                              double *d_wrench) {
-  SampleGustsCall call{s != nullptr, m != nullptr, d_wrench, B, S, n_w, b0, s0, {}, {}, m ? m->tau_force_s : 0.0, m ? m->tau_torque_s : 0.0};
-  for (int k = 0; k < 6; ++k) {
-    call.mean[k] = m ? m->mean[k] : 0.0;
-    call.sigma[k] = m ? m->sigma[k] : 0.0;
-  }
-  if (const char *why = sample_gusts_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  SampleGustsLaunch go{d_wrench, B, S, n_w, b0, s0, seed, s->consts.dt, {}, {}, m->tau_force_s, m->tau_torque_s};
-  for (int k = 0; k < 6; ++k) {
-    go.mean[k] = m->mean[k];
-    go.sigma[k] = m->sigma[k];
-  }
-  const hipError_t e = launch_sample_gusts(s->stream, go);  // (enqueued on the handle's stream; not waited for)
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_sample_gusts: ") + hipGetErrorString(e));
-  return QILQR_OK;
-}
-
-int qilqr_sample_states_device(qilqr_solver *s, const double *d_x_nom, const double *sigma12, uint64_t seed, int32_t B, int32_t S, int32_t b0,
-                               int32_t s0, uint32_t flags, double *d_x0) {
-  SampleStatesCall call{s != nullptr, sigma12 != nullptr, d_x_nom, d_x0, B, S, b0, s0, flags, {}};
-  for (int k = 0; k < 12; ++k) call.sigma[k] = sigma12 ? sigma12[k] : 0.0;
-  if (const char *why = sample_states_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  SampleStatesLaunch go{d_x_nom, d_x0, B, S, b0, s0, flags, seed, {}};
-  for (int k = 0; k < 12; ++k) go.sigma[k] = sigma12[k];
-  const hipError_t e = launch_sample_states(s->stream, go);  // (not waited for)
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_sample_states: ") + hipGetErrorString(e));
-  return QILQR_OK;
-}
-
-int qilqr_reduce_scores_device(qilqr_solver *s, const double *d_score, int32_t B, int32_t S, double *d_summary) {
-  const ReduceScoresCall call{s != nullptr, d_score, d_summary, B, S};
-  if (const char *why = reduce_scores_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  const hipError_t e = launch_reduce_scores(s->stream, ReduceScoresLaunch{d_score, d_summary, B, S});  // (not waited for)
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_reduce_scores: ") + hipGetErrorString(e));
-  return QILQR_OK;
 }
 }  // extern "C"

@@ -1,6 +1,6 @@
 // host/solver.h -- the handle (qilqr_solver) and what every other host header stands on: the thread's last error, the one function every
 // kernel launch goes through with its profiling slots and roctx ranges, the device workspace, the tiled up- and download of the host-buffer
-// entry points, and the checks of a caller's trajectories.  Part of ilqr_capi.hip's translation unit (included from there, nowhere else).
+// entry points, the scratch of one call, and the checks of a caller's trajectories and states.  Part of ilqr_capi.hip's translation unit (included from there, nowhere else).
 #pragma once
 
 namespace {
@@ -17,6 +17,17 @@ int fail(int code, const std::string &msg) {
     if (_e != hipSuccess)                                                                    \
       return fail(QILQR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));         \
   } while (0)
+
+// device memory of one call, freed on every return path (filled with HIP_TRY(hipMalloc((void **)&scratch.p, ...)))
+struct DeviceScratch {
+  double *p = nullptr;
+  DeviceScratch() = default;
+  DeviceScratch(const DeviceScratch &) = delete;
+  DeviceScratch &operator=(const DeviceScratch &) = delete;
+  ~DeviceScratch() {
+    if (p) (void)hipFree(p);
+  }
+};
 
 enum Kind { K_BACKWARD = 0, K_ROLLOUT = 1, K_LINEARIZE = 2, K_OTHER = 3, K_SOLVE = 4, K_KINDS = 5 };
 
@@ -389,6 +400,18 @@ int check_quaternions(const double *traj, long count, const char *what) {
     const double nn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     if (!(std::fabs(nn - 1.0) <= 1e-10))
       return fail(QILQR_ERR_BAD_QUATERNION, std::string(what) + ": quaternion not normalized at knot " + std::to_string(i));
+  }
+  return QILQR_OK;
+}
+// the same check of states, rows of QILQR_STATE words (the x0 of the shift and of the flights): row r is sample r % S of problem r / S;
+// S = 0: a row is a problem, and no sample is named
+int check_state_quaternions(const double *x0, long rows, long S) {
+  for (long r = 0; r < rows; ++r) {
+    const double *q = x0 + r * QILQR_STATE + 3;
+    const double nn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (!(std::fabs(nn - 1.0) <= 1e-10))
+      return fail(QILQR_ERR_BAD_QUATERNION, "x0: quaternion not normalized at problem " + std::to_string(S ? r / S : r) +
+                                                (S ? ", sample " + std::to_string(r % S) : std::string()));
   }
   return QILQR_OK;
 }

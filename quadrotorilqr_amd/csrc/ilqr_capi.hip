@@ -42,7 +42,8 @@ using namespace qilqr;
 #include "host/launches.h"      // the route of a call, refusals, begin_batch and the launch_* helpers of every kernel family
 #include "host/batch_solve.h"   // the round loops, the copy-back under the tail, sub-batch streams, the staged batch solve
 #include "host/api_handle.h"    // create, destroy, options, profiles and the extension setters
-#include "host/api_calls.h"     // qilqr_solve_batch, qilqr_solve, the stand-alone passes, pinned host memory, qilqr_shift_batch[_device], qilqr_closed_loop[_device]
+#include "host/api_calls.h"     // qilqr_solve_batch, qilqr_solve, the stand-alone passes, pinned host memory
+#include "host/caller_arrays.h" // the calls on the caller's own arrays: the shift, qilqr_backwards_pass_device, the closed-loop flights, the Monte-Carlo calls
 #include "host/sharded.h"       // one batch over several devices: the RCCL binding, the gather, every qilqr_sharded_* entry point
 #include "host/describe.h"      // qilqr_describe, qilqr_compaction_moves, the diagnostics builds' qilqr_debug_* entry points
 

@@ -1,7 +1,7 @@
 // monte_carlo.hip -- the translation unit of k_sample_gusts, k_sample_states and k_reduce_scores (monte_carlo_kernels.h), the device side
 // of qilqr_sample_gusts_device, qilqr_sample_states_device and qilqr_reduce_scores_device.  Its own unit because the three work on the
 // caller's arrays only -- no workspace, no model, no route -- and the device code of the other units stays what it was.  Exports three
-// hidden functions (monte_carlo_launch.h), which host/api_calls.h calls.
+// hidden functions (monte_carlo_launch.h), which host/caller_arrays.h calls.
 #include <hip/hip_runtime.h>
 
 #include "monte_carlo_kernels.h"

@@ -1,7 +1,7 @@
 // monte_carlo_launch.h -- what monte_carlo.hip gives the rest of the library: the launches of k_sample_gusts, k_sample_states and
 // k_reduce_scores (monte_carlo_kernels.h) for qilqr_sample_gusts_device, qilqr_sample_states_device and qilqr_reduce_scores_device, and
 // the rules of what those calls refuse.  Declarations and host code only -- no device code enters the translation unit that includes this
-// (ilqr_capi.hip through host/api_calls.h); hidden: not part of the C ABI.  The rules compile under g++
+// (ilqr_capi.hip through host/caller_arrays.h); hidden: not part of the C ABI.  The rules compile under g++
 // (tests/host_monte_carlo_harness.cpp).
 #pragma once
 
@@ -9,15 +9,13 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "ranges.h"
+
 namespace qilqr {
 
 // ---- the refusals, from facts alone (no device, no handle): null when the call is admitted, else the reason.  The arguments first, so
 // that each is refused by its own reason whatever the handle is; the handle last.
 namespace mc_rule {
-inline bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-  const char *x = (const char *)a, *y = (const char *)b;
-  return x && y && x < y + nb && y < x + na;
-}
 inline const char *shape(long B, long S, long b0, long s0) {
   if (B <= 0 || S <= 0) return "B and S must be positive";
   if (b0 < 0 || s0 < 0) return "b0 and s0 must not be negative";
@@ -35,7 +33,7 @@ inline const char *sample_gusts_refusal(const SampleGustsCall &c) {
   if (!c.model || !c.wrench) return "sample gusts: null argument (the model and d_wrench are needed)";
   if (const char *why = mc_rule::shape(c.B, c.S, c.b0, c.s0)) return why;
   if (c.n_w <= 0) return "sample gusts: n_w must be positive";
-  if ((uintptr_t)c.wrench & 15) return "sample gusts: d_wrench must be 16-byte aligned";
+  if (off_16_bytes({c.wrench})) return "sample gusts: d_wrench must be 16-byte aligned";
   for (int k = 0; k < 6; ++k) {
     if (!std::isfinite(c.mean[k])) return "sample gusts: the mean must be finite";
     if (!(c.sigma[k] >= 0.0) || !std::isfinite(c.sigma[k])) return "sample gusts: every sigma must be finite and not negative";
@@ -56,11 +54,11 @@ struct SampleStatesCall {
 inline const char *sample_states_refusal(const SampleStatesCall &c) {
   if (!c.x_nom || !c.sigma_given || !c.x0) return "sample states: null argument (d_x_nom, sigma12 and d_x0 are needed)";
   if (const char *why = mc_rule::shape(c.B, c.S, c.b0, c.s0)) return why;
-  if (((uintptr_t)c.x_nom | (uintptr_t)c.x0) & 15) return "sample states: d_x_nom and d_x0 must be 16-byte aligned";
+  if (off_16_bytes({c.x_nom, c.x0})) return "sample states: d_x_nom and d_x0 must be 16-byte aligned";
   for (int k = 0; k < 12; ++k)
     if (!(c.sigma[k] >= 0.0) || !std::isfinite(c.sigma[k])) return "sample states: every sigma must be finite and not negative";
   if (c.flags & ~1ul) return "sample states: unknown flag bits (bit 0, the first sample is the nominal state, is the only one)";
-  if (mc_rule::overlap(c.x0, sizeof(double) * 13 * (size_t)c.B * (size_t)c.S, c.x_nom, sizeof(double) * 13 * (size_t)c.B))
+  if (ranges_overlap(c.x0, sizeof(double) * 13 * (size_t)c.B * (size_t)c.S, c.x_nom, sizeof(double) * 13 * (size_t)c.B))
     return "sample states: d_x0 overlaps d_x_nom";
   if (!c.handle) return "sample states: null handle";
   return nullptr;
@@ -74,8 +72,8 @@ struct ReduceScoresCall {
 inline const char *reduce_scores_refusal(const ReduceScoresCall &c) {
   if (!c.score || !c.summary) return "reduce scores: null argument (d_score and d_summary are needed)";
   if (c.B <= 0 || c.S <= 0) return "B and S must be positive";
-  if (((uintptr_t)c.score | (uintptr_t)c.summary) & 15) return "reduce scores: d_score and d_summary must be 16-byte aligned";
-  if (mc_rule::overlap(c.summary, sizeof(double) * 8 * (size_t)c.B, c.score, sizeof(double) * 4 * (size_t)c.B * (size_t)c.S))
+  if (off_16_bytes({c.score, c.summary})) return "reduce scores: d_score and d_summary must be 16-byte aligned";
+  if (ranges_overlap(c.summary, sizeof(double) * 8 * (size_t)c.B, c.score, sizeof(double) * 4 * (size_t)c.B * (size_t)c.S))
     return "reduce scores: d_summary overlaps d_score";
   if (!c.handle) return "reduce scores: null handle";
   return nullptr;

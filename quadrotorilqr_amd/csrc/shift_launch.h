@@ -1,6 +1,6 @@
 // shift_launch.h -- the one function shift.hip gives the rest of the library: the launch of k_shift (shift_kernels.h) for one call of
 // qilqr_shift_batch[_device].  Declarations only -- no device code enters the translation unit that includes this (ilqr_capi.hip through
-// host/api_calls.h); hidden: not part of the C ABI.
+// host/caller_arrays.h); hidden: not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 """The scored closed-loop flight on the device (qilqr_closed_loop_scored[_device], k_closed_loop_scored): with nothing new asked for, the
-bits of qilqr_closed_loop_device; under gusts against the restatement from the oracle's primitives (tests/scored_flight_numpy.py); the
+bits of qilqr_closed_loop_device, and of qilqr_closed_loop in the host form; under gusts against the restatement from the oracle's primitives (tests/scored_flight_numpy.py); the
 score against qilqr_cost_trajectory on the flights themselves; across the kernel's two forms bit for bit (S = 64 and 126 share a plan's
 operands through LDS -- the score's among them -- S = 70, 5 and 1 do not); over a window of knots; through the device form's stream
 ordering; and through quadrotorilqr_amd.mpc.RecedingHorizon.evaluate.  n = 24 on closed_loop_numpy.plans."""
@@ -105,6 +105,46 @@ def test_with_the_three_new_arguments_null_it_has_the_bits_of_closed_loop_device
     # ... and so through capi
     host = s.closed_loop(plan, gains, x0)
     assert host["traj"].tobytes() == want_traj.tobytes() and host["stats"].tobytes() == want_stats.tobytes() and sorted(host) == ["stats", "traj"]
+
+
+def test_the_plain_host_form_is_the_scored_one_with_the_three_new_arguments_null():
+    """qilqr_closed_loop and qilqr_closed_loop_scored(wrench = desired = out_score = NULL) through ctypes, on a handle with thrust limits:
+    the same bytes in 0xFF-prefilled outputs in both forms of the kernel, over all knots and over a window, and the same refusals"""
+    B = 3
+    cfg, plan, s, gains = case(B)
+    s.set_control_limits(0.5, 5.0)
+    lib = capi.load()
+    plan, gains = capi._d16(plan), capi._d16(gains)
+
+    def both(handle, x0, i0, i1):
+        """[(rc, the last error, out_traj, out_stats)] of the plain and of the scored entry point"""
+        S, out = x0.shape[1], []
+        for scored in (False, True):
+            traj, stats = capi._d16(np.empty((B, S, N, 18))), capi._d16(np.empty((B, S, 4)))
+            traj.view(np.uint8)[...] = 0xFF
+            stats.view(np.uint8)[...] = 0xFF
+            head, tail = (handle._h, plan.ctypes.data, gains.ctypes.data, x0.ctypes.data), (B, N, S, i0, i1, traj.ctypes.data, stats.ctypes.data)
+            rc = lib.qilqr_closed_loop_scored(*head, None, 0, None, *tail, None) if scored else lib.qilqr_closed_loop(*head, *tail)
+            out.append((rc, lib.qilqr_last_error().decode() if rc else "", traj, stats))
+        return out
+
+    for S in (5, 64):  # the flattened and the shared-operand form
+        for i0, i1 in ((0, N - 1), (3, 17)):
+            x0 = capi._d16(cn.sample_states(plan, S, i0, SEED + 11 + i0))
+            (rc_p, _, traj_p, stats_p), (rc_s, _, traj_s, stats_s) = both(s, x0, i0, i1)
+            assert rc_p == 0 and rc_s == 0, (S, i0, i1, lib.qilqr_last_error())
+            assert traj_p.tobytes() == traj_s.tobytes() and stats_p.tobytes() == stats_s.tobytes(), (S, i0, i1)
+            raw = traj_p.view(np.uint8).reshape(B, S, N, 18 * 8)
+            assert (raw[:, :, :i0] == 0xFF).all() and (raw[:, :, i1 + 1:] == 0xFF).all(), (S, i0, i1)
+            assert not np.isnan(traj_p[:, :, i0:i1 + 1]).any() and not np.isnan(stats_p).any() and np.array_equal(traj_p[:, :, i0, 1:14], x0), (S, i0, i1)
+    # what a handle makes both refuse: the same code, the same words
+    x0 = capi._d16(cn.sample_states(plan, 5, 0, SEED + 11))
+    other_count = capi.from_config(cfg)
+    other_count.set_models([MODELS3[b % 3] for b in range(B)])  # (B models, and B * S = 15 samples)
+    for handle, why in ((capi.from_config(cfg, precision="f32"), "precision 0"), (other_count, "they were set for 3, this call has B * S = 15")):
+        (rc_p, text_p, traj_p, _), (rc_s, text_s, traj_s, _) = both(handle, x0, 0, N - 1)
+        assert rc_p == rc_s == capi.ERR_INVALID_ARG and text_p == text_s and why in text_p, (rc_p, rc_s, text_p, text_s)
+        assert (traj_p.view(np.uint8) == 0xFF).all() and (traj_s.view(np.uint8) == 0xFF).all()
 
 
 # ------------------------------------------------------------------------------------------------ 2. the restatement

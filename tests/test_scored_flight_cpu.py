@@ -384,6 +384,18 @@ def test_the_rule_of_what_a_scored_call_refuses(harness):
     assert "n_w must be" in rule(harness, n_w=2, handle=0) and "null handle" in rule(harness, handle=0, pobs_B=3)
 
 
+def test_the_plain_rule_is_the_scored_rule_without_the_new_arguments(harness):
+    """every row of tests/test_closed_loop_cpu.py's table: closed_loop_refusal says what closed_loop_scored_refusal says of the same call
+    with no wrench, no desired trajectory, no score and none of the handle's facts (closed_loop_launch.h defines the one through the other)"""
+    from tests import test_closed_loop_cpu as plain
+    plain_harness = plain.build_harness(["-O0"], "host_closed_loop_harness")
+    nothing_new = dict(out_score=0, wrench=0, desired=0, n_w=0, pobs_B=0, n_desired=0, n_sched=0, k0=0)
+    for change, why in plain.REFUSALS + [(change, "^ok$") for change in plain.ADMITTED]:
+        want = plain.rule(plain_harness, **change)
+        got = rule(harness, **dict(plain.OK_CALL, **change), **nothing_new)
+        assert got == want and re.search(why, got), (change, got, want)
+
+
 def test_the_abi_without_a_device():
     """every refusal that needs no handle, through ctypes: the arguments are looked at before the handle, so a NULL handle is the last"""
     lib = capi.load()

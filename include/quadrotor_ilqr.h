@@ -557,6 +557,67 @@ int qilqr_sample_states_device(qilqr_solver *s, const double *d_x_nom, const dou
                                int32_t b0, int32_t s0, uint32_t flags, double *d_x0);
 int qilqr_reduce_scores_device(qilqr_solver *s, const double *d_score, int32_t B, int32_t S, double *d_summary);
 
+/* Risk measures per plan and the choice among candidate plans, on the device (extension): what follows the reduction on the handle's
+ * stream when the caller asks for tail measures instead of a mean, and for the decision the samples were flown for.  Device arrays
+ * only; sharded handles have no such call (use a shard's solver).
+ *
+ * qilqr_risk_scores_device reads d_score, B x S x QILQR_CL_SCORE as the scored flight writes it, and writes d_risk,
+ * B x n_levels x QILQR_MC_RISK; levels is a host array of n_levels doubles in [0, 1).  The key of sample j of plan b is
+ *     score[b, j, 0]    for column QILQR_RISK_COST,         -score[b, j, 1]    for column QILQR_RISK_CLEARANCE
+ * so that the bad end is always the upper tail, and a NaN key counts as +inf: a diverged flight is the worst outcome here, NOT a
+ * skipped one as in word 0 of the summary.  The samples are ordered by (key, j), the sample index breaking ties.  Per level the host
+ * computes the rank in double, k = min(S - 1, max(0, ceil(level S) - 1)), and m = S - k; with t_0 <= ... <= t_(m-1) the keys at
+ * sorted positions k ... S - 1 the words are
+ *     0  t_0, the order statistic: the cost that a fraction `level` of the flights stay under (VaR); clearance column: -t_0, the
+ *        clearance that all but the worst m flights keep
+ *     1  (sum t_i) / m, the mean of the tail (CVaR); clearance column: -(sum t_i) / m, the mean of the m smallest clearances
+ *     2  the sample at sorted position k (the smaller index on equal keys)
+ *     3  m
+ * The order of the sum: lane l of one wavefront folds t_l, t_(l+64), ... in that order, and the lanes are combined by the butterfly
+ * 32, 16, 8, 4, 2, 1 with IEEE additions, as qilqr_reduce_scores_device combines its lanes; a tail that holds a +inf gives +inf.  The
+ * sum runs over SORTED positions: words 0, 1 and 3 depend on the multiset of the plan's keys only -- permuting the samples changes no
+ * bit of them -- and a plan's words depend neither on B nor on the other plans.  One block sorts a plan, so S is at most
+ * QILQR_RISK_MAX_SAMPLES.
+ *
+ * qilqr_select_plans_device chooses among candidates.  The batch is V vehicles x C candidates, candidate-major: plan b = c V + v.
+ * (The samplers' draws depend on (seed, b0 + b, s0 + s, ...): sampling each candidate's slice [c V, (c + 1) V) with b0 = 0 gives every
+ * candidate of a vehicle the same start states and gusts -- common random numbers.)  d_summary is (C V) x QILQR_MC_SUMMARY from
+ * qilqr_reduce_scores_device, d_risk (C V) x n_levels x QILQR_MC_RISK on the cost column (it may be NULL for objectives 0 and 1).  A
+ * candidate is feasible when summary[4] <= max_collision_fraction, summary[7] <= max_diverged_fraction, summary[5] >= min_clearance
+ * and its objective is not NaN.  The choice is the feasible candidate with the smallest (objective, c); without a feasible one, the
+ * smallest (collision fraction, diverged fraction, objective with NaN as +inf, c).  d_choice[v] = c, and d_info[v], QILQR_SELECT_INFO
+ * words: the chosen objective, the number of feasible candidates, the chosen collision fraction, 1.0 if the fallback chose (else 0.0).
+ * Every comparison is exact.  The gather is optional -- d_plan (C V x n x 18), d_gains (C V x n x 52), d_out_plan (V x n x 18) and
+ * d_out_gains (V x n x 52) are given all together or not at all: a second launch on the same stream that reads d_choice from device
+ * memory and copies the chosen plan and its gains word for word.
+ *
+ * Both ENQUEUE on the handle's stream and do not drain it, with the ordering rules of qilqr_closed_loop_device, and need the handle
+ * for its stream and its device only: every precision mode is accepted.  QILQR_ERR_INVALID_ARG, before the device is touched, in this
+ * order.  Risk: a NULL d_score, levels or d_risk; a non-positive B or S; S above QILQR_RISK_MAX_SAMPLES; an unknown column; n_levels
+ * outside 1 ... QILQR_RISK_MAX_LEVELS; a level that is NaN or outside [0, 1); an array off a 16-byte boundary; d_risk overlapping
+ * d_score.  Selection: a NULL d_summary, rule, d_choice or d_info; a non-positive V or C; an objective outside 0 ... 3 or, for
+ * objectives 2 and 3, n_levels or the level out of range; d_risk NULL for objective 2 or 3; a NaN threshold; an array off a 16-byte
+ * boundary; a partial set of gather pointers, or a non-positive n with a full set; an output overlapping an input or another output.
+ * Last, for both, a NULL handle. */
+#define QILQR_MC_RISK 4
+#define QILQR_RISK_MAX_LEVELS 8
+#define QILQR_RISK_MAX_SAMPLES 4096
+#define QILQR_RISK_COST 0
+#define QILQR_RISK_CLEARANCE 1
+int qilqr_risk_scores_device(qilqr_solver *s, const double *d_score, int32_t B, int32_t S, int32_t column, const double *levels,
+                             int32_t n_levels, double *d_risk);
+#define QILQR_SELECT_INFO 4
+typedef struct {
+  int32_t objective;             /* 0: summary word 0 (mean cost); 1: summary word 2 (worst finite cost); 2: risk word 0; 3: risk word 1 */
+  int32_t level;                 /* which of the risk array's levels (objectives 2 and 3) */
+  double max_collision_fraction; /* feasible: summary[4] <= this */
+  double max_diverged_fraction;  /* feasible: summary[7] <= this */
+  double min_clearance;          /* feasible: summary[5] >= this; -inf asks nothing */
+} qilqr_select_rule;
+int qilqr_select_plans_device(qilqr_solver *s, const double *d_summary, const double *d_risk, int32_t n_levels,
+                              const qilqr_select_rule *rule, int32_t V, int32_t C, int32_t *d_choice, double *d_info,
+                              const double *d_plan, const double *d_gains, int32_t n, double *d_out_plan, double *d_out_gains);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -695,7 +756,9 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * qilqr_sharded_set_horizon_start, qilqr_shift_batch, qilqr_shift_batch_device, QILQR_STATE, QILQR_TAIL_HOLD, QILQR_TAIL_HOVER,
  * qilqr_backwards_pass_device, qilqr_closed_loop, qilqr_closed_loop_device, QILQR_CL_STATS, qilqr_closed_loop_scored,
  * qilqr_closed_loop_scored_device, QILQR_WRENCH, QILQR_CL_SCORE, qilqr_sample_gusts_device, qilqr_sample_states_device,
- * qilqr_reduce_scores_device, qilqr_gust_model and QILQR_MC_SUMMARY were added within version 7: no structure changed. */
+ * qilqr_reduce_scores_device, qilqr_gust_model, QILQR_MC_SUMMARY, qilqr_risk_scores_device, qilqr_select_plans_device,
+ * qilqr_select_rule, QILQR_MC_RISK, QILQR_RISK_MAX_LEVELS, QILQR_RISK_MAX_SAMPLES, QILQR_RISK_COST, QILQR_RISK_CLEARANCE and
+ * QILQR_SELECT_INFO were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

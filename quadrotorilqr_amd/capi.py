@@ -39,6 +39,12 @@ TAILS = {"hold": 0, "hover": 1}  # QILQR_TAIL_HOLD, QILQR_TAIL_HOVER: the contro
 CL_SCORE = 4  # QILQR_CL_SCORE: cost, min clearance, knot of the min clearance, knots in collision (closed_loop with score=True)
 WRENCH = 6  # QILQR_WRENCH: F_x, F_y, F_z (world frame, N), tau_x, tau_y, tau_z (body frame, N m) of a disturbance (closed_loop's wrench)
 MC_SUMMARY = 8  # QILQR_MC_SUMMARY: mean cost, its deviation, worst cost, its sample, collision fraction, min clearance, its sample, diverged fraction
+RISK = 4  # QILQR_MC_RISK: per level the order statistic (VaR), the mean of the tail behind it (CVaR), the sample at the rank, the tail's count
+RISK_MAX_LEVELS = 8  # QILQR_RISK_MAX_LEVELS
+RISK_MAX_SAMPLES = 4096  # QILQR_RISK_MAX_SAMPLES: one block sorts a plan's samples
+RISK_COLUMNS = {"cost": 0, "clearance": 1}  # QILQR_RISK_COST, QILQR_RISK_CLEARANCE
+SELECT_INFO = 4  # QILQR_SELECT_INFO: the chosen objective, the number of feasible candidates, the chosen collision fraction, 1.0 if the fallback chose
+SELECT_OBJECTIVES = {"mean": 0, "worst": 1, "var": 2, "cvar": 3}  # qilqr_select_rule.objective: summary words 0 and 2, risk words 0 and 1
 CL_STATS = 4  # QILQR_CL_STATS: max position error, max rotation error, |dx| at the last knot, clamped (knot, rotor) pairs (closed_loop)
 
 # every symbol include/quadrotor_ilqr.h declares
@@ -53,6 +59,7 @@ EXPORTS = (
     "qilqr_backwards_pass_device", "qilqr_closed_loop", "qilqr_closed_loop_device",
     "qilqr_closed_loop_scored", "qilqr_closed_loop_scored_device",
     "qilqr_sample_gusts_device", "qilqr_sample_states_device", "qilqr_reduce_scores_device",
+    "qilqr_risk_scores_device", "qilqr_select_plans_device",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -82,6 +89,11 @@ class DeviceConfig(C.Structure):
 
 class GustModel(C.Structure):
     _fields_ = [("mean", C.c_double * 6), ("sigma", C.c_double * 6), ("tau_force_s", C.c_double), ("tau_torque_s", C.c_double)]
+
+
+class SelectRule(C.Structure):
+    _fields_ = [("objective", C.c_int32), ("level", C.c_int32), ("max_collision_fraction", C.c_double), ("max_diverged_fraction", C.c_double),
+                ("min_clearance", C.c_double)]
 
 
 class Profile(C.Structure):
@@ -138,6 +150,9 @@ def load():
         lib.qilqr_sample_gusts_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_int32] * 5 + [C.c_void_p]
         lib.qilqr_sample_states_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_int32] * 4 + [C.c_uint32, C.c_void_p]
         lib.qilqr_reduce_scores_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        lib.qilqr_risk_scores_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        lib.qilqr_select_plans_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + \
+            [C.c_int32, C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -747,6 +762,62 @@ class QuadrotorILQRBatch:
         if wait_current_stream:
             self._wait_current_stream(score)
         _check(load().qilqr_reduce_scores_device(self._h, C.c_void_p(score.data_ptr()), C.c_int32(B), C.c_int32(S), C.c_void_p(out.data_ptr())))
+
+    # ---- behind the reduction: tail measures per plan, and the choice among a vehicle's candidate plans
+    def risk_scores_device(self, score, out, levels, column="cost", wait_current_stream=True):
+        """qilqr_risk_scores_device: out (B, L, 4) from score (B, S, 4) as closed_loop_device's out_score holds it, S <= 4096: per level of
+        `levels` (L <= 8 numbers in [0, 1)) the order statistic of the cost at rank ceil(level S) - 1 (VaR), the mean of the tail from
+        there on (CVaR), the sample at the rank and the tail's count; column="clearance": of the clearance, the lower tail (the clearance
+        all but the worst flights keep, the mean of the smallest).  A NaN counts as the worst outcome.  ENQUEUED on the solver's own
+        stream and not waited for."""
+        if score is None or score.dim() != 3:
+            raise TypeError(f"score must be (B, S, {CL_SCORE})")
+        if column not in RISK_COLUMNS:
+            raise TypeError("column must be 'cost' or 'clearance'")
+        B, S = int(score.shape[0]), int(score.shape[1])
+        lv = np.ascontiguousarray(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+        if lv.ndim != 1 or not 1 <= len(lv) <= RISK_MAX_LEVELS:
+            raise TypeError(f"levels must be 1 ... {RISK_MAX_LEVELS} numbers")
+        self._device_tensors(((score, "score", (B, S, CL_SCORE)), (out, "out", (B, len(lv), RISK))), required=("out",))
+        if wait_current_stream:
+            self._wait_current_stream(score)
+        _check(load().qilqr_risk_scores_device(self._h, C.c_void_p(score.data_ptr()), C.c_int32(B), C.c_int32(S), C.c_int32(RISK_COLUMNS[column]),
+                                               C.c_void_p(lv.ctypes.data), C.c_int32(len(lv)), C.c_void_p(out.data_ptr())))
+
+    def select_plans_device(self, summary, C, choice, info, objective="cvar", level=0, risk=None, max_collision_fraction=1.0, max_diverged_fraction=1.0,
+                            min_clearance=-np.inf, plan=None, gains=None, out_plan=None, out_gains=None, wait_current_stream=True):
+        """qilqr_select_plans_device: of the C candidate plans of each of V vehicles (summary (C V, 8) from reduce_scores_device, plan
+        b = c V + v; risk (C V, L, 4) from risk_scores_device on the cost column) the feasible one -- collision fraction, diverged fraction
+        and smallest clearance within the three thresholds, objective not NaN -- with the smallest objective ("mean", "worst": summary words
+        0 and 2; "var", "cvar": words 0 and 1 of the risk array's `level`), the smaller candidate on ties; without a feasible one the
+        smallest (collision fraction, diverged fraction, objective, c).  choice (V,) int32 and info (V, 4) receive the candidate and
+        {its objective, the number of feasible candidates, its collision fraction, 1.0 if the fallback chose}.  plan (C V, n, 18), gains
+        (C V, n, 52), out_plan (V, n, 18) and out_gains (V, n, 52), all four or none: the chosen plans and their gains are gathered.
+        ENQUEUED on the solver's own stream and not waited for."""
+        import ctypes as ct  # (C is the number of candidates here, as in the C ABI)
+        import torch
+        if summary is None or summary.dim() != 2:
+            raise TypeError(f"summary must be (C V, {MC_SUMMARY})")
+        cands = int(C)
+        if cands <= 0 or int(summary.shape[0]) % cands:
+            raise TypeError(f"summary has {int(summary.shape[0])} plans: not a multiple of {cands} candidates")
+        if objective not in SELECT_OBJECTIVES:
+            raise TypeError("objective must be one of " + ", ".join(SELECT_OBJECTIVES))
+        V = int(summary.shape[0]) // cands
+        L = 0 if risk is None else (int(risk.shape[1]) if risk.dim() == 3 else -1)
+        gather = [t for t in (plan, gains, out_plan, out_gains) if t is not None]
+        if len(gather) not in (0, 4):
+            raise TypeError("plan, gains, out_plan and out_gains are given all together or not at all")
+        n = int(plan.shape[1]) if gather and plan.dim() == 3 else 0
+        self._device_tensors(((summary, "summary", (cands * V, MC_SUMMARY)), (risk, "risk", (cands * V, L, RISK)), (choice, "choice", (V,), torch.int32),
+                              (info, "info", (V, SELECT_INFO)), (plan, "plan", (cands * V, n, KNOT)), (gains, "gains", (cands * V, n, GAIN)),
+                              (out_plan, "out_plan", (V, n, KNOT)), (out_gains, "out_gains", (V, n, GAIN))), required=("choice", "info"))
+        rule = SelectRule(SELECT_OBJECTIVES[objective], int(level), float(max_collision_fraction), float(max_diverged_fraction), float(min_clearance))
+        if wait_current_stream:
+            self._wait_current_stream(summary)
+        vp = lambda t: ct.c_void_p(0 if t is None else t.data_ptr())
+        _check(load().qilqr_select_plans_device(self._h, vp(summary), vp(risk), ct.c_int32(max(L, 0)), ct.byref(rule), ct.c_int32(V), ct.c_int32(cands), vp(choice),
+                                                vp(info), vp(plan), vp(gains), ct.c_int32(n), vp(out_plan), vp(out_gains)))
 
     def profile_get(self):
         p = Profile()

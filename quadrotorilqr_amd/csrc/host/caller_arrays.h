@@ -1,7 +1,8 @@
 // host/caller_arrays.h -- the C ABI of the calls that work on the caller's own arrays and use no workspace, no BatchState and no route: the
 // receding-horizon shift (k_shift: shift.hip), the backward pass over device arrays, the closed-loop flights of a plan (k_closed_loop and
-// k_closed_loop_scored: closed_loop.hip, closed_loop_scored.hip) and the ends of the Monte-Carlo loop (monte_carlo.hip).  Each call has
-// one refusal (from the rules of ranges.h, closed_loop_launch.h and monte_carlo_launch.h), one enqueue, a device form that enqueues and
+// k_closed_loop_scored: closed_loop.hip, closed_loop_scored.hip), the ends of the Monte-Carlo loop (monte_carlo.hip) and the risk
+// measures and the choice among candidate plans behind it (risk.hip).  Each call has
+// one refusal (from the rules of ranges.h, closed_loop_launch.h, monte_carlo_launch.h and risk_launch.h), one enqueue, a device form that enqueues and
 // returns, and -- the shift and the flight -- a host form that stages the arrays through one DeviceScratch.  Part of ilqr_capi.hip's
 // translation unit.
 #pragma once
@@ -272,6 +273,36 @@ int qilqr_reduce_scores_device(qilqr_solver *s, const double *d_score, int32_t B
   HIP_TRY(hipSetDevice(s->device));
   const hipError_t e = launch_reduce_scores(s->stream, ReduceScoresLaunch{d_score, d_summary, B, S});  // (not waited for)
   if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_reduce_scores: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+// ---- behind the reduction: tail measures per plan and the choice among a vehicle's candidates (k_risk_scores, k_select_plans and
+// k_gather_plans: risk_kernels.h, compiled by risk.hip).  The handle gives its stream and its device; the rules are risk_launch.h's.
+static_assert(QILQR_MC_RISK == 4 && QILQR_RISK_MAX_LEVELS == 8 && QILQR_RISK_MAX_SAMPLES == 4096 && QILQR_RISK_COST == 0 && QILQR_RISK_CLEARANCE == 1 &&
+                  QILQR_SELECT_INFO == 4,
+              "risk_kernels.h, risk_launch.h and the C header agree on the words of a level, the caps and the columns");
+int qilqr_risk_scores_device(qilqr_solver *s, const double *d_score, int32_t B, int32_t S, int32_t column, const double *levels, int32_t n_levels,
+                             double *d_risk) {
+  const RiskScoresCall call{s != nullptr, d_score, d_risk, levels, B, S, column, n_levels};
+  if (const char *why = risk_scores_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
+  HIP_TRY(hipSetDevice(s->device));
+  const hipError_t e = launch_risk_scores(s->stream, RiskScoresLaunch{d_score, d_risk, B, S, column, n_levels, levels});  // (not waited for)
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_risk_scores: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+
+int qilqr_select_plans_device(qilqr_solver *s, const double *d_summary, const double *d_risk, int32_t n_levels, const qilqr_select_rule *rule, int32_t V,
+                              int32_t C, int32_t *d_choice, double *d_info, const double *d_plan, const double *d_gains, int32_t n, double *d_out_plan,
+                              double *d_out_gains) {
+  const SelectPlansCall call{s != nullptr, rule != nullptr, rule ? rule->objective : 0, rule ? rule->level : 0, rule ? rule->max_collision_fraction : 0.0,
+                             rule ? rule->max_diverged_fraction : 0.0, rule ? rule->min_clearance : 0.0, d_summary, d_risk, d_choice, d_info, d_plan, d_gains,
+                             d_out_plan, d_out_gains, n_levels, V, C, n};
+  if (const char *why = select_plans_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
+  HIP_TRY(hipSetDevice(s->device));
+  const bool risky = rule->objective >= 2;
+  const SelectPlansLaunch go{d_summary, risky ? d_risk : nullptr, d_choice, d_info, risky ? n_levels : 0, V, C, rule->objective, rule->level,
+                             rule->max_collision_fraction, rule->max_diverged_fraction, rule->min_clearance, d_plan, d_gains, d_out_plan, d_out_gains, n};
+  const hipError_t e = launch_select_plans(s->stream, go);  // (one or two launches; not waited for)
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_select_plans: ") + hipGetErrorString(e));
   return QILQR_OK;
 }
 }  // extern "C"

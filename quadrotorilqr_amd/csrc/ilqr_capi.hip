@@ -34,6 +34,7 @@
 #include "shift_launch.h"
 #include "closed_loop_launch.h"
 #include "monte_carlo_launch.h"
+#include "risk_launch.h"
 
 using namespace qilqr;
 
@@ -43,7 +44,7 @@ using namespace qilqr;
 #include "host/batch_solve.h"   // the round loops, the copy-back under the tail, sub-batch streams, the staged batch solve
 #include "host/api_handle.h"    // create, destroy, options, profiles and the extension setters
 #include "host/api_calls.h"     // qilqr_solve_batch, qilqr_solve, the stand-alone passes, pinned host memory
-#include "host/caller_arrays.h" // the calls on the caller's own arrays: the shift, qilqr_backwards_pass_device, the closed-loop flights, the Monte-Carlo calls
+#include "host/caller_arrays.h" // the calls on the caller's own arrays: the shift, qilqr_backwards_pass_device, the closed-loop flights, the Monte-Carlo calls, risk and selection
 #include "host/sharded.h"       // one batch over several devices: the RCCL binding, the gather, every qilqr_sharded_* entry point
 #include "host/describe.h"      // qilqr_describe, qilqr_compaction_moves, the diagnostics builds' qilqr_debug_* entry points
 

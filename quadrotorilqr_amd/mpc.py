@@ -44,6 +44,10 @@ class RecedingHorizon:
         self._eval = None                # evaluate()'s buffers for the last S: (S, n_w, x0, wrench, stats, score)
         self._mc = None                  # evaluate_sampled()'s for the last (S, n_w): (S, n_w, x_nom, x0, wrench, stats, score, summary)
         self.sampled = None              # ... and what its last call sampled: (x0 (B, S, 13), wrench (B, S, n_w, 6) or None), its buffers
+        self._risk = None                # evaluate_sampled()'s risk array (B, L, 4) for the last L
+        self._last = None                # what select() works on: (summary, risk or None, its column) of the last evaluate_sampled()
+        self._pad = None                 # evaluate_sampled()'s copies with padded candidates: (C, S, x_nom (C, V + 1, 13), x0 (C, V S + 1, 13) or None)
+        self._sel = None                 # select()'s outputs for the last C: (C, choice, info, plan, gains)
 
     def _to_device(self, a, dst):
         import torch
@@ -135,7 +139,7 @@ class RecedingHorizon:
         torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
         return dict(stats=d_stats, score=d_score)
 
-    def evaluate_sampled(self, x, S, seed, state_sigma, gust=None, n_w=None, first_is_nominal=True):
+    def evaluate_sampled(self, x, S, seed, state_sigma, gust=None, n_w=None, first_is_nominal=True, risk_levels=None, risk_column="cost", candidates=1):
         """The Monte-Carlo loop about the last plan without the host: S start states per plan sampled about the measured states x (B, 13;
         NumPy or torch) with deviations state_sigma (12 words over [rho, theta, dv, dw], or one number), gusts sampled from `gust` (None: no
         disturbance; else a dict with the fields of qilqr_gust_model -- sigma, and optionally mean, tau_force_s, tau_torque_s) for n_w
@@ -143,7 +147,12 @@ class RecedingHorizon:
         Four enqueues on the solver's stream, then torch's current stream waits once.  first_is_nominal: sample 0 starts at x itself.
         Returns {"stats": (B, S, 4), "score": (B, S, 4), "summary": (B, 8)} (QuadrotorILQRBatch.reduce_scores_device's words): device
         tensors this object owns, valid until the next call with another S or n_w.  The sampled states and wrenches stay in
-        `self.sampled` = (x0, wrench).  Needs the gains of the last plan, as evaluate()."""
+        `self.sampled` = (x0, wrench).  Needs the gains of the last plan, as evaluate().
+        risk_levels (up to 8 numbers in [0, 1); S <= 4096): the result also carries "risk", (B, L, 4) -- per level the order statistic
+        (VaR) and the tail mean (CVaR) of the cost, or with risk_column="clearance" of the clearance (QuadrotorILQRBatch.risk_scores_device's
+        words), one more enqueue behind the reduction.  candidates = C (B divisible by C): the batch is B / C vehicles x C candidate plans,
+        plan b = c V + v, and the samplers are called once per candidate on its V plans with plan offset 0, so that every candidate of a
+        vehicle flies the same sampled start states (about its own row of x) and gusts -- common random numbers; select() then chooses."""
         import torch
         if not self._have_gains:
             raise RuntimeError("evaluate_sampled() needs the gains of the last plan: call start() or tick() with gains=True")
@@ -158,17 +167,80 @@ class RecedingHorizon:
             self._mc = (S, n_w, new(self.B, capi.STATE), new(self.B, S, capi.STATE), new(self.B, S, n_w, capi.WRENCH) if n_w else None,
                         new(self.B, S, capi.CL_STATS), new(self.B, S, capi.CL_SCORE), new(self.B, capi.MC_SUMMARY))
         _, _, d_nom, d_x0, d_w, d_stats, d_score, d_sum = self._mc
+        C = int(candidates)
+        if C <= 0 or self.B % C:
+            raise TypeError(f"candidates must divide B = {self.B}")
+        levels = None if risk_levels is None else np.atleast_1d(np.asarray(risk_levels, dtype=np.float64))
+        if levels is not None and (self._risk is None or self._risk.shape[1] != len(levels)):
+            self._risk = torch.zeros((self.B, len(levels), capi.RISK), dtype=torch.float64, device=self.device)
+        self._last = None
         self._to_device(x, d_nom)  # (on torch's current stream: the first enqueue below makes the solver's stream wait for it)
-        self.solver.sample_states_device(d_nom, d_x0, seed, state_sigma, first_is_nominal=first_is_nominal)
-        if d_w is not None:
-            self.solver.sample_gusts_device(d_w, seed, gust["sigma"], gust.get("mean"), gust.get("tau_force_s", 0.0), gust.get("tau_torque_s", 0.0),
-                                            wait_current_stream=False)
+        V = self.B // C
+        # A candidate's V plans are contiguous: slices of the buffers (one candidate: the whole batch).  The calls want 16-byte
+        # boundaries, and a row of 13 words puts a slice with an odd number of rows before it 8 bytes off one: the measured states, and the
+        # sampled ones when V S is odd, then go through a copy whose candidates lie one row further apart.
+        nom_of = x0_of = None
+        if C > 1 and V % 2:
+            if self._pad is None or self._pad[:2] != (C, S):  # (kept: the solver's stream reads them after this returns)
+                new = lambda rows: torch.zeros((C, rows, capi.STATE), dtype=torch.float64, device=self.device)
+                self._pad = (C, S, new(V + 1), new(V * S + 1) if S % 2 else None)
+            nom_pad, x0_pad = self._pad[2:]
+            nom_pad[:, :V].copy_(d_nom.view(C, V, capi.STATE))  # (torch's current stream, before the first enqueue)
+            nom_of = lambda c: nom_pad[c, :V]
+            if x0_pad is not None:
+                x0_of = lambda c: x0_pad[c, :V * S].view(V, S, capi.STATE)
+        for c in range(C):
+            rows = slice(c * V, (c + 1) * V)
+            self.solver.sample_states_device(nom_of(c) if nom_of else d_nom[rows], x0_of(c) if x0_of else d_x0[rows], seed, state_sigma,
+                                             first_is_nominal=first_is_nominal, wait_current_stream=c == 0)
+            if d_w is not None:
+                self.solver.sample_gusts_device(d_w[rows], seed, gust["sigma"], gust.get("mean"), gust.get("tau_force_s", 0.0), gust.get("tau_torque_s", 0.0),
+                                                wait_current_stream=False)
+        if x0_of:
+            with torch.cuda.stream(self._stream):  # (behind the samplers, before the flight: the solver's own stream)
+                d_x0.view(C, V * S, capi.STATE).copy_(x0_pad[:, :V * S])
         self.solver.closed_loop_device(self._buf[self._cur], self.gains, d_x0, out_stats=d_stats, wrench=d_w, out_score=d_score, wait_current_stream=False)
         self.solver.reduce_scores_device(d_score, d_sum, wait_current_stream=False)
-        # (all four enqueued on the solver's stream, in order, and none waited for: torch's stream waits once, behind the last)
+        res = dict(stats=d_stats, score=d_score, summary=d_sum)
+        if levels is not None:
+            self.solver.risk_scores_device(d_score, self._risk, levels, column=risk_column, wait_current_stream=False)
+            res["risk"] = self._risk
+        # (all enqueued on the solver's stream, in order, and none waited for: torch's stream waits once, behind the last)
         torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
         self.sampled = (d_x0, d_w)
-        return dict(stats=d_stats, score=d_score, summary=d_sum)
+        self._last = (d_sum, self._risk if levels is not None else None, risk_column)
+        return res
+
+    def select(self, C, objective="cvar", level=0, max_collision_fraction=1.0, max_diverged_fraction=1.0, min_clearance=-np.inf):
+        """The choice among the C candidate plans of each of the B / C vehicles (plan b = c V + v) from the last evaluate_sampled() result
+        (QuadrotorILQRBatch.select_plans_device: the feasible candidate with the smallest objective -- "mean", "worst", or "var", "cvar" at
+        `level` of that call's risk_levels, which must have been on the cost column -- else the fallback order), and the gather of the
+        chosen plans and their gains.  Returns {"choice": (V,) int32, "info": (V, 4), "plan": (V, n, 18), "gains": (V, n, 52), "u0": (V, 4),
+        a view of the plan}: device tensors this object owns (valid until the next select with another C), complete on torch's current
+        stream after one wait."""
+        import torch
+        if self._last is None or not self._have_gains:
+            raise RuntimeError("select() works on the last evaluate_sampled() result: call it first")
+        C = int(C)
+        if C <= 0 or self.B % C:
+            raise TypeError(f"C must divide B = {self.B}")
+        d_sum, d_risk, column = self._last
+        risky = objective in ("var", "cvar")
+        if risky and d_risk is None:
+            raise RuntimeError(f"objective {objective!r} needs evaluate_sampled(..., risk_levels=...)")
+        if risky and column != "cost":
+            raise RuntimeError(f"objective {objective!r} needs the risk of the cost column, not of {column!r}")
+        V = self.B // C
+        if self._sel is None or self._sel[0] != C:
+            new = lambda *s, dtype=torch.float64: torch.zeros(s, dtype=dtype, device=self.device)
+            self._sel = (C, new(V, dtype=torch.int32), new(V, capi.SELECT_INFO), new(V, self.n, capi.KNOT), new(V, self.n, capi.GAIN))
+        _, d_choice, d_info, d_plan, d_gains = self._sel
+        self.solver.select_plans_device(d_sum, C, d_choice, d_info, objective=objective, level=level, risk=d_risk if risky else None,
+                                        max_collision_fraction=max_collision_fraction, max_diverged_fraction=max_diverged_fraction, min_clearance=min_clearance,
+                                        plan=self._buf[self._cur], gains=self.gains, out_plan=d_plan, out_gains=d_gains)
+        # (two launches on the solver's stream; torch's stream waits once, behind the gather)
+        torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
+        return dict(choice=d_choice, info=d_info, plan=d_plan, gains=d_gains, u0=d_plan[:, 0, 14:18])
 
     def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False, gains=False):
         """One control tick: the horizon start advanced by `steps` (advance=False: the desired trajectory is relative to the vehicle and

@@ -10,6 +10,8 @@
 //       and limits -- what S = 1, x0 = plan[:, 0, 1:14], i0 = 0, i1 = n - 1 must reproduce bit for bit
 //   host_closed_loop_harness refuse plan gains x0 out_traj out_stats B n S i0 i1 handle f32 modeled models_B
 //       (addresses and numbers in decimal) prints the reason, or "ok"
+//   host_closed_loop_harness form S...
+//       prints, for every S, "shared" or "flattened": closed_loop_shared_form(S), the rule of the kernel's two forms
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -104,6 +106,10 @@ int run_refuse(char **a) {
 int main(int argc, char **argv) {
   if (argc == 4 && !std::strcmp(argv[1], "fly")) return run_fly(argv[2], argv[3]);
   if (argc == 16 && !std::strcmp(argv[1], "refuse")) return run_refuse(argv + 2);
-  std::fprintf(stderr, "usage: %s fly IN OUT | refuse plan gains x0 out_traj out_stats B n S i0 i1 handle f32 modeled models_B\n", argv[0]);
+  if (argc >= 3 && !std::strcmp(argv[1], "form")) {
+    for (int k = 2; k < argc; ++k) std::puts(closed_loop_shared_form(std::atoi(argv[k])) ? "shared" : "flattened");
+    return 0;
+  }
+  std::fprintf(stderr, "usage: %s fly IN OUT | refuse plan gains x0 out_traj out_stats B n S i0 i1 handle f32 modeled models_B | form S...\n", argv[0]);
   return 1;
 }

@@ -618,6 +618,56 @@ int qilqr_select_plans_device(qilqr_solver *s, const double *d_summary, const do
                               const qilqr_select_rule *rule, int32_t V, int32_t C, int32_t *d_choice, double *d_info,
                               const double *d_plan, const double *d_gains, int32_t n, double *d_out_plan, double *d_out_gains);
 
+/* A sampling planner on the device (extension; MPPI / path-integral control): the Monte-Carlo loop's generator, flight and score turned
+ * on the plan's controls, and the samples fed back into the plan.  Device arrays only; sharded handles have no such call.
+ *
+ * qilqr_mppi_flight_device flies S control-perturbed copies of each of B plans OPEN LOOP and writes d_score, B x S x QILQR_CL_SCORE --
+ * the layout of the scored closed-loop flight, so qilqr_reduce_scores_device and qilqr_risk_scores_device work on it unchanged.  Sample
+ * (b, j) starts at d_x0[b] (QILQR_STATE words; d_x0 NULL: words 1..13 of knot 0 of plan b) and at knots i = 0 .. n - 1 applies
+ *     u_i = d_plan[b, i, 14:18] + eps_i,   clamped to the thrust limits while they are set (the clamped control is scored and stepped with)
+ * where eps_i[a], rotor a, is the recursion of qilqr_sample_gusts_device per rotor -- g_0 = sigma[a] xi_0, g_i = fma(rho, g_{i-1},
+ * kappa_a xi_i) with rho = tau_s > 0 ? exp(-dt / tau_s) : 0 and kappa_a = sigma[a] sqrt((1 - rho)(1 + rho)) -- over the normals of draw
+ * (seed; b0 + b, j, row i, stream 2, pair a / 2), normal a % 2.  With QILQR_MPPI_FIRST_IS_NOMINAL sample 0 flies eps = 0.  A knot is
+ * scored as qilqr_closed_loop_scored scores it (the handle's Q or schedule from its horizon start, R, d_desired -- B x n x 18, one per
+ * plan -- or the handle's desired trajectory, the shared and the per-problem spheres), and stepped with the handle's integrator and,
+ * while per-problem models are set (for B problems), the model of plan b.  No perturbation is ever stored: it is a function of its indices.
+ *
+ * qilqr_mppi_update_device moves each plan's controls to the weighted mean perturbation and leaves a consistent trajectory in
+ * d_out_plan, B x n x 18.  With J_j = cost_j + collision_cost hits_j (words 0 and 3 of d_score[b, j]; a key that is not finite has
+ * weight 0), J_min the smallest finite key (the smaller j on ties) and w_j = exp(-(J_j - J_min) / lambda):
+ *     eta = sum_j w_j,    du_i[a] = (sum_j w_j eps_j,i[a]) / eta,    u_i[a] = clamp(d_plan[b, i, 14 + a] + du_i[a])
+ * with eps REDRAWN from the same indices (as drawn, not as clamped; rule, seed, S and b0 must be the flight's).  Without a finite key the
+ * controls are the plan's, bit for bit.  Every sum has one order: with T the power of two >= S (64 at the least, 1024 at the most) lane
+ * t folds samples t, t + T, ... in that order, the 64 lanes of a wavefront combine by the butterfly 32, 16, 8, 4, 2, 1, the wavefronts in
+ * index order; a term w_j eps is rounded before it is added.  A plan's bits depend on neither B nor its neighbours.  A second launch
+ * flies the new controls from x0 with eps = 0, writes the flown states into d_out_plan -- a valid initial trajectory for
+ * qilqr_solve_batch_device -- and scores that flight.  d_info[b], QILQR_MPPI_INFO words:
+ *     0  J_min (NaN without a finite key)          2  the effective sample size eta^2 / sum_j w_j^2 (0 without)
+ *     1  the sample at J_min (-1 without)          3  the number of finite keys          4 .. 7  the four score words of the new plan
+ *
+ * Both ENQUEUE on the handle's stream and do not drain it, with the ordering rules of qilqr_closed_loop_device.
+ * QILQR_ERR_INVALID_ARG, before the device is touched, in this order: a NULL rule, d_plan or d_score (the update: or d_out_plan, d_info);
+ * B, n or S not positive, or n < 2; S above QILQR_RISK_MAX_SAMPLES; a negative b0; a sigma that is NaN or negative; lambda not > 0;
+ * a tau_s or collision_cost that is NaN or negative; unknown flag bits or reserved != 0; an array off a 16-byte boundary; the flight's
+ * d_score or the update's d_out_plan overlapping an input; d_info overlapping anything; a NULL handle; then, as the scored closed-loop
+ * flight, a handle in a mixed-precision mode, per-problem models or spheres set for another B, and (QILQR_ERR_LENGTH_MISMATCH) knots
+ * beyond the handle's desired trajectory or schedule. */
+#define QILQR_MPPI_INFO 8
+#define QILQR_MPPI_FIRST_IS_NOMINAL 1u
+typedef struct {
+  double   sigma[4];        /* N per rotor: deviation of the control perturbation, >= 0 */
+  double   tau_s;           /* correlation time along the horizon; 0: white (as qilqr_gust_model) */
+  double   lambda;          /* temperature of the weights, > 0 */
+  double   collision_cost;  /* added to a sample's key per knot in collision, >= 0 */
+  uint32_t flags;           /* QILQR_MPPI_FIRST_IS_NOMINAL = 1: sample 0 flies eps = 0 */
+  uint32_t reserved;        /* 0 */
+} qilqr_mppi_rule;          /* 64 bytes */
+int qilqr_mppi_flight_device(qilqr_solver *s, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0,
+                             const double *d_desired, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_score);
+int qilqr_mppi_update_device(qilqr_solver *s, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0,
+                             const double *d_desired, const double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0,
+                             double *d_out_plan, double *d_info);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -757,8 +807,9 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * qilqr_backwards_pass_device, qilqr_closed_loop, qilqr_closed_loop_device, QILQR_CL_STATS, qilqr_closed_loop_scored,
  * qilqr_closed_loop_scored_device, QILQR_WRENCH, QILQR_CL_SCORE, qilqr_sample_gusts_device, qilqr_sample_states_device,
  * qilqr_reduce_scores_device, qilqr_gust_model, QILQR_MC_SUMMARY, qilqr_risk_scores_device, qilqr_select_plans_device,
- * qilqr_select_rule, QILQR_MC_RISK, QILQR_RISK_MAX_LEVELS, QILQR_RISK_MAX_SAMPLES, QILQR_RISK_COST, QILQR_RISK_CLEARANCE and
- * QILQR_SELECT_INFO were added within version 7: no structure changed. */
+ * qilqr_select_rule, QILQR_MC_RISK, QILQR_RISK_MAX_LEVELS, QILQR_RISK_MAX_SAMPLES, QILQR_RISK_COST, QILQR_RISK_CLEARANCE,
+ * QILQR_SELECT_INFO, qilqr_mppi_flight_device, qilqr_mppi_update_device, qilqr_mppi_rule, QILQR_MPPI_INFO and
+ * QILQR_MPPI_FIRST_IS_NOMINAL were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

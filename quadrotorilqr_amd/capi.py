@@ -45,6 +45,8 @@ RISK_MAX_SAMPLES = 4096  # QILQR_RISK_MAX_SAMPLES: one block sorts a plan's samp
 RISK_COLUMNS = {"cost": 0, "clearance": 1}  # QILQR_RISK_COST, QILQR_RISK_CLEARANCE
 SELECT_INFO = 4  # QILQR_SELECT_INFO: the chosen objective, the number of feasible candidates, the chosen collision fraction, 1.0 if the fallback chose
 SELECT_OBJECTIVES = {"mean": 0, "worst": 1, "var": 2, "cvar": 3}  # qilqr_select_rule.objective: summary words 0 and 2, risk words 0 and 1
+MPPI_INFO = 8  # QILQR_MPPI_INFO: J_min, its sample, the effective sample size, the finite samples, the four score words of the new plan (mppi_update_device)
+MPPI_FIRST_IS_NOMINAL = 1  # QILQR_MPPI_FIRST_IS_NOMINAL: qilqr_mppi_rule.flags, sample 0 flies the plan's own controls
 CL_STATS = 4  # QILQR_CL_STATS: max position error, max rotation error, |dx| at the last knot, clamped (knot, rotor) pairs (closed_loop)
 
 # every symbol include/quadrotor_ilqr.h declares
@@ -60,6 +62,7 @@ EXPORTS = (
     "qilqr_closed_loop_scored", "qilqr_closed_loop_scored_device",
     "qilqr_sample_gusts_device", "qilqr_sample_states_device", "qilqr_reduce_scores_device",
     "qilqr_risk_scores_device", "qilqr_select_plans_device",
+    "qilqr_mppi_flight_device", "qilqr_mppi_update_device",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -94,6 +97,11 @@ class GustModel(C.Structure):
 class SelectRule(C.Structure):
     _fields_ = [("objective", C.c_int32), ("level", C.c_int32), ("max_collision_fraction", C.c_double), ("max_diverged_fraction", C.c_double),
                 ("min_clearance", C.c_double)]
+
+
+class MppiRule(C.Structure):
+    _fields_ = [("sigma", C.c_double * 4), ("tau_s", C.c_double), ("lambda_", C.c_double), ("collision_cost", C.c_double), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class Profile(C.Structure):
@@ -153,6 +161,8 @@ def load():
         lib.qilqr_risk_scores_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         lib.qilqr_select_plans_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + \
             [C.c_int32, C.c_void_p, C.c_void_p]
+        lib.qilqr_mppi_flight_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]
+        lib.qilqr_mppi_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p] * 2
         _lib = lib
     return _lib
 
@@ -322,6 +332,15 @@ def gust_model(sigma, mean=None, tau_force_s=0.0, tau_torque_s=0.0):
     m.mean[:] = six(0.0 if mean is None else mean, "mean")
     m.tau_force_s, m.tau_torque_s = float(tau_force_s), float(tau_torque_s)
     return m
+
+
+def mppi_rule(sigma, lambda_, tau_s=0.0, collision_cost=0.0, first_is_nominal=True):
+    """a qilqr_mppi_rule: sigma one number for the four rotors or four, N; lambda_ the temperature of the weights"""
+    sig = np.atleast_1d(np.asarray(sigma, dtype=np.float64))
+    sig = np.repeat(sig, 4) if sig.shape == (1,) else sig
+    if sig.shape != (4,):
+        raise TypeError("sigma must have 1 or 4 words")
+    return MppiRule((C.c_double * 4)(*sig), float(tau_s), float(lambda_), float(collision_cost), MPPI_FIRST_IS_NOMINAL if first_is_nominal else 0, 0)
 
 
 def _tail(tail):
@@ -818,6 +837,49 @@ class QuadrotorILQRBatch:
         vp = lambda t: ct.c_void_p(0 if t is None else t.data_ptr())
         _check(load().qilqr_select_plans_device(self._h, vp(summary), vp(risk), ct.c_int32(max(L, 0)), ct.byref(rule), ct.c_int32(V), ct.c_int32(cands), vp(choice),
                                                 vp(info), vp(plan), vp(gains), ct.c_int32(n), vp(out_plan), vp(out_gains)))
+
+    # ---- the sampling planner: control-perturbed flights of a plan, and the plan moved to their weighted mean
+    def _mppi_tensors(self, plan, x0, desired, score):
+        if plan is None or plan.dim() != 3 or plan.shape[2] != KNOT:
+            raise TypeError("plan must be (B, n, 18)")
+        if score is None or score.dim() != 3:
+            raise TypeError(f"score must be (B, S, {CL_SCORE})")
+        B, n, S = int(plan.shape[0]), int(plan.shape[1]), int(score.shape[1])
+        self._device_tensors(((plan, "plan", (B, n, KNOT)), (x0, "x0", (B, STATE)), (desired, "desired", (B, n, KNOT)), (score, "score", (B, S, CL_SCORE))))
+        return B, n, S
+
+    def mppi_flight_device(self, plan, score, seed, sigma, lambda_=1.0, tau_s=0.0, collision_cost=0.0, first_is_nominal=True, x0=None, desired=None, b0=0,
+                           wait_current_stream=True):
+        """qilqr_mppi_flight_device on torch tensors: S = score.shape[1] copies of each plan of plan (B, n, 18) flown open loop from x0 (B, 13;
+        None: the plan's knot 0) under u_i = clamp(plan_u_i + eps_i), eps a Gauss-Markov perturbation per rotor of deviation sigma (one
+        number or four, N) and correlation time tau_s (0: white) drawn from (seed, b0 + b, sample, knot), and scored as closed_loop_device
+        scores a flight (desired (B, n, 18): against it instead of the handle's desired trajectory) into score (B, S, 4) -- what
+        reduce_scores_device and risk_scores_device read.  first_is_nominal: sample 0 flies the plan's own controls.  lambda_ and
+        collision_cost are the update's and only checked here.  ENQUEUED on the solver's own stream and not waited for."""
+        B, n, S = self._mppi_tensors(plan, x0, desired, score)
+        rule = mppi_rule(sigma, lambda_, tau_s, collision_cost, first_is_nominal)
+        if wait_current_stream:
+            self._wait_current_stream(plan)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        _check(load().qilqr_mppi_flight_device(self._h, C.byref(rule), C.c_uint64(int(seed)), vp(plan), vp(x0), vp(desired), C.c_int32(B), C.c_int32(n),
+                                               C.c_int32(S), C.c_int32(int(b0)), vp(score)))
+
+    def mppi_update_device(self, plan, score, out_plan, info, seed, sigma, lambda_, tau_s=0.0, collision_cost=0.0, first_is_nominal=True, x0=None,
+                           desired=None, b0=0, wait_current_stream=True):
+        """qilqr_mppi_update_device on torch tensors: from the scores (B, S, 4) of mppi_flight_device called with the same plan, seed, sigma,
+        tau_s, first_is_nominal, x0, desired and b0, out_plan (B, n, 18) receives the plan with its controls moved to the weighted mean
+        perturbation -- weights exp(-(J - J_min) / lambda_), J = cost + collision_cost * knots in collision, the perturbations redrawn --
+        clamped to the thrust limits, and its states flown from x0 under those controls: a trajectory solve_batch_device accepts as its
+        initial one.  info (B, 8): J_min, its sample, the effective sample size, the samples with a finite J, and the four score words of the
+        new plan.  ENQUEUED on the solver's own stream (two launches) and not waited for."""
+        B, n, S = self._mppi_tensors(plan, x0, desired, score)
+        self._device_tensors(((out_plan, "out_plan", (B, n, KNOT)), (info, "info", (B, MPPI_INFO))), required=("out_plan", "info"))
+        rule = mppi_rule(sigma, lambda_, tau_s, collision_cost, first_is_nominal)
+        if wait_current_stream:
+            self._wait_current_stream(plan)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        _check(load().qilqr_mppi_update_device(self._h, C.byref(rule), C.c_uint64(int(seed)), vp(plan), vp(x0), vp(desired), vp(score), C.c_int32(B),
+                                               C.c_int32(n), C.c_int32(S), C.c_int32(int(b0)), vp(out_plan), vp(info)))
 
     def profile_get(self):
         p = Profile()

@@ -1,8 +1,8 @@
 // host/caller_arrays.h -- the C ABI of the calls that work on the caller's own arrays and use no workspace, no BatchState and no route: the
 // receding-horizon shift (k_shift: shift.hip), the backward pass over device arrays, the closed-loop flights of a plan (k_closed_loop and
 // k_closed_loop_scored: closed_loop.hip, closed_loop_scored.hip), the ends of the Monte-Carlo loop (monte_carlo.hip) and the risk
-// measures and the choice among candidate plans behind it (risk.hip).  Each call has
-// one refusal (from the rules of ranges.h, closed_loop_launch.h, monte_carlo_launch.h and risk_launch.h), one enqueue, a device form that enqueues and
+// measures and the choice among candidate plans behind it (risk.hip), and the sampling planner (mppi.hip).  Each call has
+// one refusal (from the rules of ranges.h, closed_loop_launch.h, monte_carlo_launch.h, risk_launch.h and mppi_launch.h), one enqueue, a device form that enqueues and
 // returns, and -- the shift and the flight -- a host form that stages the arrays through one DeviceScratch.  Part of ilqr_capi.hip's
 // translation unit.
 #pragma once
@@ -75,6 +75,31 @@ int closed_loop_refuse(const qilqr_solver *s, const double *plan, const double *
   if (s && s->modeled && !s->f32 && s->models_B != (long)B * S) text += ": they were set for " + std::to_string(s->models_B) + ", this call has B * S = " + std::to_string((long)B * S);
   return fail(QILQR_ERR_INVALID_ARG, text);
 }
+// what a score reads of the handle, for a launch record `call` that has ClosedLoopScoredLaunch's fields of the score (that one, and
+// MppiLaunch): the desired trajectory (the caller's per plan, or the handle's from its horizon start), the state weights, the two sphere tables
+template <typename Launch>
+int score_operands(qilqr_solver *s, const double *d_desired, int32_t n, Launch &call) {
+  call.d_desired = d_desired ? d_desired : (const double *)s->d_desired + 18 * (size_t)s->k0;
+  call.desired_step = d_desired ? 18l * n : 0;
+  if (s->n_sched > 0) {
+    call.d_q = s->d_qsched + (size_t)SCHED_WORDS * s->k0;
+    call.q_step = SCHED_WORDS;
+  } else {
+    if (!s->d_cl_q) {  // (Q lies 8 bytes off a 16-byte boundary inside ModelConsts: a copy of its own, made once; the handle's Q never changes)
+      HIP_TRY(hipMalloc((void **)&s->d_cl_q, sizeof(double) * 144));
+      HIP_TRY(hipMemcpyAsync(s->d_cl_q, s->consts.Q, sizeof(double) * 144, hipMemcpyHostToDevice, s->stream));
+    }
+    call.d_q = s->d_cl_q;
+    call.q_step = 0;
+  }
+  call.d_shared = s->n_obstacles > 0 ? s->d_obstacles : nullptr;
+  call.n_shared = s->n_obstacles;
+  call.d_own = s->pobs_B > 0 ? s->d_pobs : nullptr;
+  call.d_own_counts = s->pobs_B > 0 ? s->d_pobs_counts : nullptr;
+  call.own_K = s->pobs_K;
+  return QILQR_OK;
+}
+
 int closed_loop_enqueue(qilqr_solver *s, const char *kernel, const double *d_plan, const double *d_gains, const double *d_x0, const double *d_wrench,
                         int32_t n_w, const double *d_desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1, double *d_out_traj,
                         double *d_out_stats, double *d_out_score) {
@@ -84,26 +109,8 @@ int closed_loop_enqueue(qilqr_solver *s, const char *kernel, const double *d_pla
   call.d_wrench = d_wrench;
   call.n_w = n_w;
   call.d_out_score = d_out_score;
-  if (d_out_score) {
-    call.d_desired = d_desired ? d_desired : (const double *)s->d_desired + 18 * (size_t)s->k0;
-    call.desired_step = d_desired ? 18l * n : 0;
-    if (s->n_sched > 0) {
-      call.d_q = s->d_qsched + (size_t)SCHED_WORDS * s->k0;
-      call.q_step = SCHED_WORDS;
-    } else {
-      if (!s->d_cl_q) {  // (Q lies 8 bytes off a 16-byte boundary inside ModelConsts: a copy of its own, made once; the handle's Q never changes)
-        HIP_TRY(hipMalloc((void **)&s->d_cl_q, sizeof(double) * 144));
-        HIP_TRY(hipMemcpyAsync(s->d_cl_q, s->consts.Q, sizeof(double) * 144, hipMemcpyHostToDevice, s->stream));
-      }
-      call.d_q = s->d_cl_q;
-      call.q_step = 0;
-    }
-    call.d_shared = s->n_obstacles > 0 ? s->d_obstacles : nullptr;
-    call.n_shared = s->n_obstacles;
-    call.d_own = s->pobs_B > 0 ? s->d_pobs : nullptr;
-    call.d_own_counts = s->pobs_B > 0 ? s->d_pobs_counts : nullptr;
-    call.own_K = s->pobs_K;
-  }
+  if (d_out_score)
+    if (int rc = score_operands(s, d_desired, n, call)) return rc;
   const hipError_t e = launch_closed_loop_scored(s->stream, s->consts, call);
   if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(e));
   return QILQR_OK;
@@ -304,5 +311,62 @@ int qilqr_select_plans_device(qilqr_solver *s, const double *d_summary, const do
   const hipError_t e = launch_select_plans(s->stream, go);  // (one or two launches; not waited for)
   if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_select_plans: ") + hipGetErrorString(e));
   return QILQR_OK;
+}
+}  // extern "C"
+
+// ---- the sampling planner: k_mppi_flight and k_mppi_update (mppi_kernels.h, compiled by mppi.hip) on the caller's device arrays.  ONE
+// call: the flight is the update without d_out_plan and d_info.  The rule is mppi_launch.h's; the handle gives what it gives a scored flight.
+namespace {
+int mppi_device(qilqr_solver *s, bool update, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0, const double *d_desired,
+                double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_out_plan, double *d_info) {
+  MppiCall call{};
+  call.update = update;
+  call.rule = rule != nullptr;
+  if (rule) {
+    for (int a = 0; a < 4; ++a) call.sigma[a] = rule->sigma[a];
+    call.tau_s = rule->tau_s;
+    call.lambda = rule->lambda;
+    call.collision_cost = rule->collision_cost;
+    call.flags = rule->flags;
+    call.reserved = rule->reserved;
+  }
+  call.plan = d_plan; call.x0 = d_x0; call.desired = d_desired; call.score = d_score; call.out_plan = d_out_plan; call.info = d_info;
+  call.B = B; call.n = n; call.S = S; call.b0 = b0;
+  call.handle = s != nullptr;
+  if (s) {
+    call.f32 = s->f32; call.modeled = s->modeled; call.models_B = s->models_B; call.pobs_B = s->pobs_B;
+    call.n_desired = s->n_desired; call.n_sched = s->n_sched; call.k0 = s->k0;
+  }
+  bool length = false;
+  if (const char *why = mppi_refusal(call, &length)) return fail(length ? QILQR_ERR_LENGTH_MISMATCH : QILQR_ERR_INVALID_ARG, why);
+  HIP_TRY(hipSetDevice(s->device));
+  MppiLaunch go{};
+  go.d_plan = d_plan; go.d_x0 = d_x0; go.d_score = d_score; go.d_out_plan = d_out_plan; go.d_info = d_info;
+  go.B = B; go.n = n; go.S = S; go.b0 = b0;
+  go.seed = seed;
+  for (int a = 0; a < 4; ++a) go.sigma[a] = rule->sigma[a];
+  go.tau_s = rule->tau_s; go.lambda = rule->lambda; go.collision_cost = rule->collision_cost; go.flags = rule->flags;
+  go.integrator = s->integrator;
+  go.limits = s->limited ? &s->limits : nullptr;
+  go.d_models = s->modeled ? s->d_models : nullptr;
+  if (int rc = score_operands(s, d_desired, n, go)) return rc;
+  // (enqueued on the handle's stream; not waited for)
+  const hipError_t e = update ? launch_mppi_update(s->stream, s->consts, go) : launch_mppi_flight(s->stream, s->consts, go);
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string(update ? "k_mppi_update: " : "k_mppi_flight: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+}  // namespace
+
+extern "C" {
+static_assert(QILQR_MPPI_INFO == 8 && QILQR_MPPI_FIRST_IS_NOMINAL == 1 && sizeof(qilqr_mppi_rule) == 64,
+              "mppi_kernels.h, mppi_launch.h and the C header agree on the words of a plan's info, the flag and the rule");
+int qilqr_mppi_flight_device(qilqr_solver *s, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0,
+                             const double *d_desired, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_score) {
+  return mppi_device(s, false, rule, seed, d_plan, d_x0, d_desired, d_score, B, n, S, b0, nullptr, nullptr);
+}
+int qilqr_mppi_update_device(qilqr_solver *s, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0,
+                             const double *d_desired, const double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_out_plan,
+                             double *d_info) {
+  return mppi_device(s, true, rule, seed, d_plan, d_x0, d_desired, const_cast<double *>(d_score), B, n, S, b0, d_out_plan, d_info);
 }
 }  // extern "C"

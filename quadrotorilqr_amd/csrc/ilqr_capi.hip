@@ -35,6 +35,7 @@
 #include "closed_loop_launch.h"
 #include "monte_carlo_launch.h"
 #include "risk_launch.h"
+#include "mppi_launch.h"
 
 using namespace qilqr;
 

@@ -24,7 +24,7 @@ namespace qilqr {
 
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;  // the multipliers
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;  // the Weyl constants: golden ratio, sqrt(3) - 1
-constexpr uint32_t MC_STREAM_GUSTS = 0, MC_STREAM_STATES = 1;
+constexpr uint32_t MC_STREAM_GUSTS = 0, MC_STREAM_STATES = 1, MC_STREAM_CONTROLS = 2;
 
 // c <- Philox4x32-10(c; k)
 QILQR_HD void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {

@@ -13,7 +13,8 @@ Between two ticks the plan can be flown closed loop: tick(x0, gains=True) also l
 (QuadrotorILQRBatch.backwards_pass_device), and control(x, i) evaluates the law u = u_i + K_i (x (-) plan_i) at measured states
 (closed_loop_device with one sample per plan and i0 = i1 = i); evaluate(x0, wrench) flies S sampled states per plan under that law -- and
 under sampled disturbances -- and returns the statistics and the score of every flight (closed_loop_device with out_score), on device
-buffers.
+buffers.  Ahead of a solve, start / tick(..., explore=dict(S=, seed=, sigma=, lambda_=)) runs rounds of the sampling planner on the
+shifted plan (mppi_flight_device, mppi_update_device): the solve then polishes what the samples found.
 """
 import numpy as np
 
@@ -48,6 +49,7 @@ class RecedingHorizon:
         self._last = None                # what select() works on: (summary, risk or None, its column) of the last evaluate_sampled()
         self._pad = None                 # evaluate_sampled()'s copies with padded candidates: (C, S, x_nom (C, V + 1, 13), x0 (C, V S + 1, 13) or None)
         self._sel = None                 # select()'s outputs for the last C: (C, choice, info, plan, gains)
+        self._mppi = None                # _explore()'s buffers for the last S: (S, a scratch plan (B, n, 18), score (B, S, 4), info (B, 8))
 
     def _to_device(self, a, dst):
         import torch
@@ -82,13 +84,43 @@ class RecedingHorizon:
             res["gains"] = self.gains
         return res
 
-    def start(self, init, keep_init=False, gains=False):
+    def _explore(self, explore):
+        """`iterations` rounds of the sampling planner on the plan in the current buffer, before its solve: S control-perturbed flights
+        from the plan's knot 0 (QuadrotorILQRBatch.mppi_flight_device) and the plan moved to their weighted mean (mppi_update_device),
+        out of the current buffer into a scratch buffer, which then becomes the current one.  Enqueued on the solver's stream, behind
+        torch's current stream, and not waited for: the solve that follows is ordered behind it.  Returns the last round's info (B, 8)."""
+        import torch
+        known = {"S", "seed", "sigma", "lambda_", "tau_s", "collision_cost", "iterations", "first_is_nominal"}
+        if not isinstance(explore, dict) or not {"S", "seed", "sigma", "lambda_"} <= set(explore) or set(explore) - known:
+            raise TypeError("explore must be a dict with S, seed, sigma, lambda_ and optionally tau_s, collision_cost, iterations, first_is_nominal")
+        S, rounds = int(explore["S"]), int(explore.get("iterations", 1))
+        if S <= 0 or rounds <= 0:
+            raise TypeError("explore: S and iterations must be positive")
+        if self._mppi is None or self._mppi[0] != S:
+            new = lambda *s: torch.zeros(s, dtype=torch.float64, device=self.device)
+            self._mppi = (S, new(self.B, self.n, capi.KNOT), new(self.B, S, capi.CL_SCORE), new(self.B, capi.MPPI_INFO))
+        _, scratch, d_score, d_info = self._mppi
+        kw = dict(tau_s=explore.get("tau_s", 0.0), collision_cost=explore.get("collision_cost", 0.0), first_is_nominal=explore.get("first_is_nominal", True))
+        for r in range(rounds):
+            src, seed = self._buf[self._cur], int(explore["seed"]) + r  # (a round's draws are its own)
+            self.solver.mppi_flight_device(src, d_score, seed, explore["sigma"], explore["lambda_"], wait_current_stream=r == 0, **kw)
+            self.solver.mppi_update_device(src, d_score, scratch, d_info, seed, explore["sigma"], explore["lambda_"], wait_current_stream=False, **kw)
+            self._buf[self._cur], scratch = scratch, src
+            self._mppi = (S, scratch, d_score, d_info)
+        return d_info
+
+    def start(self, init, keep_init=False, gains=False, explore=None):
         """A plain solve of `init` (B, n, 18; NumPy or torch) from the start of the handle's desired trajectory (horizon start 0).
-        gains=True: as for tick."""
+        gains=True, explore: as for tick."""
         self.solver.set_horizon_start(0)
         self.k0 = 0
         self._to_device(init, self._buf[self._cur])
-        return self._solve(keep_init, gains)
+        if explore is None:
+            return self._solve(keep_init, gains)
+        info = self._explore(explore)
+        res = self._solve(keep_init, gains)
+        res["explore"] = info
+        return res
 
     def control(self, x, i=0):
         """The (B, 4) controls of the last plan's feedback law at knot `i` for the measured states x (B, 13; NumPy or torch):
@@ -242,7 +274,7 @@ class RecedingHorizon:
         torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
         return dict(choice=d_choice, info=d_info, plan=d_plan, gains=d_gains, u0=d_plan[:, 0, 14:18])
 
-    def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False, gains=False):
+    def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False, gains=False, explore=None):
         """One control tick: the horizon start advanced by `steps` (advance=False: the desired trajectory is relative to the vehicle and
         stays), the last plan shifted into the other buffer with knot 0 at x0 (B, 13; NumPy or torch; None keeps the plan's own), and the
         solve from there.  Returns views (valid until the next tick but one) of the first controls u0 = traj[:, 0, 14:18], the plan, cost,
@@ -250,7 +282,11 @@ class RecedingHorizon:
         the solve started from in `self.init`: made on torch's current stream, which is made to wait for the shift on the solver's stream
         first (the two streams are ordered with each other only where one is told to wait).  gains=True also leaves the feedback gains about
         the new plan in `self.gains` (B, n, 52; a device buffer this object owns, allocated at the first such call) and returns them under
-        "gains": one more backward pass on the plan (backwards_pass_device), what control() evaluates.  A tick that is refused -- steps or tail out of
+        "gains": one more backward pass on the plan (backwards_pass_device), what control() evaluates.  explore (None: nothing changes): a dict
+        with S, seed, sigma, lambda_ and optionally tau_s, collision_cost, iterations (1) and first_is_nominal (True) -- between the shift
+        and the solve `iterations` rounds of the sampling planner run on the solver's stream (_explore: round r with seed + r, S perturbed
+        flights from knot 0 and the plan moved to their weighted mean, through a scratch buffer), the solve polishes what they found, and
+        the result carries "explore", the last round's info (B, 8; QuadrotorILQRBatch.mppi_update_device's words).  A tick that is refused -- steps or tail out of
         range, or no window of n knots left behind the new start -- raises and leaves the object and the handle's start as they were."""
         steps = int(steps)
         x0 = None if x0 is None else self._to_device(x0, self._x0)
@@ -263,7 +299,12 @@ class RecedingHorizon:
                 self.solver.set_horizon_start(had_k0 + steps)
                 self.k0 = had_k0 + steps
             self._cur ^= 1
-            return self._solve(keep_init, gains)
+            if explore is None:
+                return self._solve(keep_init, gains)
+            info = self._explore(explore)
+            res = self._solve(keep_init, gains)
+            res["explore"] = info
+            return res
         except Exception:
             # a refused start or solve (past the end of the mission no window of n knots is left) leaves the last plan, its buffer and the
             # start it was solved at in force

@@ -668,6 +668,42 @@ int qilqr_mppi_update_device(qilqr_solver *s, const qilqr_mppi_rule *rule, uint6
                              const double *d_desired, const double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0,
                              double *d_out_plan, double *d_info);
 
+/* The planner's spread per plan, knot and rotor, adapted on the device (extension; covariance adaptation of the MPPI / CEM family, the
+ * diagonal only).  A SPREAD is a device array d_spread, B x n x 4 doubles: the deviation, N, of the perturbation of plan b at knot i,
+ * rotor a.  A caller initialises it (from rule->sigma, say); rule->sigma is checked as before and NOT read for the draws.
+ *
+ * qilqr_mppi_flight_spread_device is qilqr_mppi_flight_device with
+ *     eps_i[a] = d_spread[b, i, a] * z_i[a]   (a rounded product),   z the recursion above with sigma = {1, 1, 1, 1}:
+ *     z_0 = xi_0,  z_i = fma(rho, z_{i-1}, kappa1 xi_i),  kappa1 = sqrt((1 - rho)(1 + rho))
+ * over the same draws.  With tau_s = 0 and d_spread[b, i, a] = sigma[a] everywhere d_score has the bits of qilqr_mppi_flight_device.
+ *
+ * qilqr_mppi_adapt_device is qilqr_mppi_update_device (the same keys, weights, eta, fold orders, d_out_plan and d_info, the same second
+ * launch) over those perturbations, and also writes d_out_spread, B x n x 4 (NULL: the mean only).  Per knot and rotor, with the sums
+ * in the update's order and every product rounded before it is added:
+ *     m1 = sum_j w_j eps,   m2 = sum_j (w_j eps) eps,   du = m1 / eta,   var = m2 / eta - du du   (not > 0: 0)
+ *     v = (1 - rate) s_old^2 + rate var,   s_new = sqrt(v) clamped to [floor[a], cap[a]]
+ * Without a finite key controls and spread are the inputs', bit for bit.  The call does not work in place.  Nothing is checked on the
+ * device: a NaN spread gives NaN controls, a NaN cost and weight 0.
+ *
+ * Both ENQUEUE on the handle's stream and do not drain it.  QILQR_ERR_INVALID_ARG: what the two calls above refuse of the common
+ * arguments, in their order and before the handle is looked at; then a NULL d_spread (the adaptation: or a NULL adapt); a floor that is
+ * NaN or negative; a cap that is NaN, infinite or below its floor; a rate not in (0, 1]; a nonzero reserved word; d_spread or
+ * d_out_spread off a 16-byte boundary; d_out_spread overlapping an input (d_spread among them), d_out_plan or d_info; the flight's
+ * d_score or the adaptation's d_out_plan or d_info overlapping d_spread; then the NULL handle and the handle's reasons as above. */
+typedef struct {
+  double floor[4];     /* N per rotor: the smallest deviation a new spread may have, >= 0 */
+  double cap[4];       /* the largest; finite, >= floor */
+  double rate;         /* in (0, 1]: new variance = (1 - rate) old + rate weighted */
+  double reserved[3];  /* 0 */
+} qilqr_mppi_adapt_rule;   /* 96 bytes */
+int qilqr_mppi_flight_spread_device(qilqr_solver *s, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0,
+                                    const double *d_desired, const double *d_spread, int32_t B, int32_t n, int32_t S, int32_t b0,
+                                    double *d_score);
+int qilqr_mppi_adapt_device(qilqr_solver *s, const qilqr_mppi_rule *rule, const qilqr_mppi_adapt_rule *adapt, uint64_t seed,
+                            const double *d_plan, const double *d_x0, const double *d_desired, const double *d_spread,
+                            const double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_out_plan,
+                            double *d_out_spread, double *d_info);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -808,8 +844,9 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * qilqr_closed_loop_scored_device, QILQR_WRENCH, QILQR_CL_SCORE, qilqr_sample_gusts_device, qilqr_sample_states_device,
  * qilqr_reduce_scores_device, qilqr_gust_model, QILQR_MC_SUMMARY, qilqr_risk_scores_device, qilqr_select_plans_device,
  * qilqr_select_rule, QILQR_MC_RISK, QILQR_RISK_MAX_LEVELS, QILQR_RISK_MAX_SAMPLES, QILQR_RISK_COST, QILQR_RISK_CLEARANCE,
- * QILQR_SELECT_INFO, qilqr_mppi_flight_device, qilqr_mppi_update_device, qilqr_mppi_rule, QILQR_MPPI_INFO and
- * QILQR_MPPI_FIRST_IS_NOMINAL were added within version 7: no structure changed. */
+ * QILQR_SELECT_INFO, qilqr_mppi_flight_device, qilqr_mppi_update_device, qilqr_mppi_rule, QILQR_MPPI_INFO,
+ * QILQR_MPPI_FIRST_IS_NOMINAL, qilqr_mppi_flight_spread_device, qilqr_mppi_adapt_device and qilqr_mppi_adapt_rule were added within
+ * version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

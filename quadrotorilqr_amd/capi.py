@@ -62,7 +62,7 @@ EXPORTS = (
     "qilqr_closed_loop_scored", "qilqr_closed_loop_scored_device",
     "qilqr_sample_gusts_device", "qilqr_sample_states_device", "qilqr_reduce_scores_device",
     "qilqr_risk_scores_device", "qilqr_select_plans_device",
-    "qilqr_mppi_flight_device", "qilqr_mppi_update_device",
+    "qilqr_mppi_flight_device", "qilqr_mppi_update_device", "qilqr_mppi_flight_spread_device", "qilqr_mppi_adapt_device",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -102,6 +102,10 @@ class SelectRule(C.Structure):
 class MppiRule(C.Structure):
     _fields_ = [("sigma", C.c_double * 4), ("tau_s", C.c_double), ("lambda_", C.c_double), ("collision_cost", C.c_double), ("flags", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class MppiAdaptRule(C.Structure):
+    _fields_ = [("floor", C.c_double * 4), ("cap", C.c_double * 4), ("rate", C.c_double), ("reserved", C.c_double * 3)]
 
 
 class Profile(C.Structure):
@@ -163,6 +167,8 @@ def load():
             [C.c_int32, C.c_void_p, C.c_void_p]
         lib.qilqr_mppi_flight_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]
         lib.qilqr_mppi_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p] * 2
+        lib.qilqr_mppi_flight_spread_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
+        lib.qilqr_mppi_adapt_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 3
         _lib = lib
     return _lib
 
@@ -341,6 +347,17 @@ def mppi_rule(sigma, lambda_, tau_s=0.0, collision_cost=0.0, first_is_nominal=Tr
     if sig.shape != (4,):
         raise TypeError("sigma must have 1 or 4 words")
     return MppiRule((C.c_double * 4)(*sig), float(tau_s), float(lambda_), float(collision_cost), MPPI_FIRST_IS_NOMINAL if first_is_nominal else 0, 0)
+
+
+def mppi_adapt_rule(floor, cap, rate):
+    """a qilqr_mppi_adapt_rule: floor and cap one number for the four rotors or four, N; rate in (0, 1]"""
+    def four(v, name):
+        v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        v = np.repeat(v, 4) if v.shape == (1,) else v
+        if v.shape != (4,):
+            raise TypeError(f"{name} must have 1 or 4 words")
+        return (C.c_double * 4)(*v)
+    return MppiAdaptRule(four(floor, "floor"), four(cap, "cap"), float(rate), (C.c_double * 3)(0.0, 0.0, 0.0))
 
 
 def _tail(tail):
@@ -880,6 +897,38 @@ class QuadrotorILQRBatch:
         vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
         _check(load().qilqr_mppi_update_device(self._h, C.byref(rule), C.c_uint64(int(seed)), vp(plan), vp(x0), vp(desired), vp(score), C.c_int32(B),
                                                C.c_int32(n), C.c_int32(S), C.c_int32(int(b0)), vp(out_plan), vp(info)))
+
+    def mppi_flight_spread_device(self, plan, spread, score, seed, sigma, lambda_=1.0, tau_s=0.0, collision_cost=0.0, first_is_nominal=True, x0=None,
+                                  desired=None, b0=0, wait_current_stream=True):
+        """qilqr_mppi_flight_spread_device on torch tensors: mppi_flight_device with the perturbation's deviation read per plan, knot and
+        rotor from spread (B, n, 4), N -- eps = spread * z, z the recursion of unit deviation over the same draws.  sigma is checked as
+        before and not read for the draws.  ENQUEUED on the solver's own stream and not waited for."""
+        B, n, S = self._mppi_tensors(plan, x0, desired, score)
+        self._device_tensors(((spread, "spread", (B, n, 4)),), required=("spread",))
+        rule = mppi_rule(sigma, lambda_, tau_s, collision_cost, first_is_nominal)
+        if wait_current_stream:
+            self._wait_current_stream(plan)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        _check(load().qilqr_mppi_flight_spread_device(self._h, C.byref(rule), C.c_uint64(int(seed)), vp(plan), vp(x0), vp(desired), vp(spread), C.c_int32(B),
+                                                      C.c_int32(n), C.c_int32(S), C.c_int32(int(b0)), vp(score)))
+
+    def mppi_adapt_device(self, plan, spread, score, out_plan, out_spread, info, seed, sigma, lambda_, floor, cap, rate, tau_s=0.0, collision_cost=0.0,
+                          first_is_nominal=True, x0=None, desired=None, b0=0, wait_current_stream=True):
+        """qilqr_mppi_adapt_device on torch tensors: mppi_update_device over the scores (B, S, 4) of mppi_flight_spread_device called with
+        the same plan, spread, seed, tau_s, first_is_nominal, x0, desired and b0 -- out_plan (B, n, 18) and info (B, 8) as the update
+        makes them -- and out_spread (B, n, 4; None: the mean only), the spread blended towards the weighted deviation of the
+        perturbations: new variance = (1 - rate) old + rate weighted, its root clamped to [floor, cap] (one number or four, N).  Not in
+        place.  ENQUEUED on the solver's own stream (two launches) and not waited for."""
+        B, n, S = self._mppi_tensors(plan, x0, desired, score)
+        self._device_tensors(((spread, "spread", (B, n, 4)), (out_plan, "out_plan", (B, n, KNOT)), (out_spread, "out_spread", (B, n, 4)),
+                              (info, "info", (B, MPPI_INFO))), required=("spread", "out_plan", "info"))
+        rule = mppi_rule(sigma, lambda_, tau_s, collision_cost, first_is_nominal)
+        adapt = mppi_adapt_rule(floor, cap, rate)
+        if wait_current_stream:
+            self._wait_current_stream(plan)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        _check(load().qilqr_mppi_adapt_device(self._h, C.byref(rule), C.byref(adapt), C.c_uint64(int(seed)), vp(plan), vp(x0), vp(desired), vp(spread),
+                                              vp(score), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(b0)), vp(out_plan), vp(out_spread), vp(info)))
 
     def profile_get(self):
         p = Profile()

@@ -1,8 +1,8 @@
 // host/caller_arrays.h -- the C ABI of the calls that work on the caller's own arrays and use no workspace, no BatchState and no route: the
 // receding-horizon shift (k_shift: shift.hip), the backward pass over device arrays, the closed-loop flights of a plan (k_closed_loop and
 // k_closed_loop_scored: closed_loop.hip, closed_loop_scored.hip), the ends of the Monte-Carlo loop (monte_carlo.hip) and the risk
-// measures and the choice among candidate plans behind it (risk.hip), and the sampling planner (mppi.hip).  Each call has
-// one refusal (from the rules of ranges.h, closed_loop_launch.h, monte_carlo_launch.h, risk_launch.h and mppi_launch.h), one enqueue, a device form that enqueues and
+// measures and the choice among candidate plans behind it (risk.hip), and the sampling planner (mppi.hip, mppi_adapt.hip).  Each call has
+// one refusal (from the rules of ranges.h, closed_loop_launch.h, monte_carlo_launch.h, risk_launch.h, mppi_launch.h and mppi_adapt_launch.h), one enqueue, a device form that enqueues and
 // returns, and -- the shift and the flight -- a host form that stages the arrays through one DeviceScratch.  Part of ilqr_capi.hip's
 // translation unit.
 #pragma once
@@ -317,8 +317,9 @@ int qilqr_select_plans_device(qilqr_solver *s, const double *d_summary, const do
 // ---- the sampling planner: k_mppi_flight and k_mppi_update (mppi_kernels.h, compiled by mppi.hip) on the caller's device arrays.  ONE
 // call: the flight is the update without d_out_plan and d_info.  The rule is mppi_launch.h's; the handle gives what it gives a scored flight.
 namespace {
-int mppi_device(qilqr_solver *s, bool update, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0, const double *d_desired,
-                double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_out_plan, double *d_info) {
+// the facts of a call for mppi_launch.h's rule
+MppiCall mppi_call_of(const qilqr_solver *s, bool update, const qilqr_mppi_rule *rule, const double *d_plan, const double *d_x0, const double *d_desired,
+                      const double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, const double *d_out_plan, const double *d_info) {
   MppiCall call{};
   call.update = update;
   call.rule = rule != nullptr;
@@ -337,10 +338,11 @@ int mppi_device(qilqr_solver *s, bool update, const qilqr_mppi_rule *rule, uint6
     call.f32 = s->f32; call.modeled = s->modeled; call.models_B = s->models_B; call.pobs_B = s->pobs_B;
     call.n_desired = s->n_desired; call.n_sched = s->n_sched; call.k0 = s->k0;
   }
-  bool length = false;
-  if (const char *why = mppi_refusal(call, &length)) return fail(length ? QILQR_ERR_LENGTH_MISMATCH : QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  MppiLaunch go{};
+  return call;
+}
+// the launch record of an admitted call
+int mppi_launch_of(qilqr_solver *s, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0, const double *d_desired,
+                   double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_out_plan, double *d_info, MppiLaunch &go) {
   go.d_plan = d_plan; go.d_x0 = d_x0; go.d_score = d_score; go.d_out_plan = d_out_plan; go.d_info = d_info;
   go.B = B; go.n = n; go.S = S; go.b0 = b0;
   go.seed = seed;
@@ -349,10 +351,58 @@ int mppi_device(qilqr_solver *s, bool update, const qilqr_mppi_rule *rule, uint6
   go.integrator = s->integrator;
   go.limits = s->limited ? &s->limits : nullptr;
   go.d_models = s->modeled ? s->d_models : nullptr;
-  if (int rc = score_operands(s, d_desired, n, go)) return rc;
+  return score_operands(s, d_desired, n, go);
+}
+
+int mppi_device(qilqr_solver *s, bool update, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0, const double *d_desired,
+                double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_out_plan, double *d_info) {
+  const MppiCall call = mppi_call_of(s, update, rule, d_plan, d_x0, d_desired, d_score, B, n, S, b0, d_out_plan, d_info);
+  bool length = false;
+  if (const char *why = mppi_refusal(call, &length)) return fail(length ? QILQR_ERR_LENGTH_MISMATCH : QILQR_ERR_INVALID_ARG, why);
+  HIP_TRY(hipSetDevice(s->device));
+  MppiLaunch go{};
+  if (int rc = mppi_launch_of(s, rule, seed, d_plan, d_x0, d_desired, d_score, B, n, S, b0, d_out_plan, d_info, go)) return rc;
   // (enqueued on the handle's stream; not waited for)
   const hipError_t e = update ? launch_mppi_update(s->stream, s->consts, go) : launch_mppi_flight(s->stream, s->consts, go);
   if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string(update ? "k_mppi_update: " : "k_mppi_flight: ") + hipGetErrorString(e));
+  return QILQR_OK;
+}
+
+// the same two calls with the deviations per plan, knot and rotor (k_mppi_flight_spread and k_mppi_adapt: mppi_adapt_kernels.h, compiled
+// by mppi_adapt.hip); the rule is mppi_adapt_launch.h's, which applies mppi_launch.h's first
+int mppi_spread_device(qilqr_solver *s, bool adapting, const qilqr_mppi_rule *rule, const qilqr_mppi_adapt_rule *adapt, uint64_t seed, const double *d_plan,
+                       const double *d_x0, const double *d_desired, const double *d_spread, double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0,
+                       double *d_out_plan, double *d_out_spread, double *d_info) {
+  MppiSpreadCall call{};
+  call.base = mppi_call_of(s, adapting, rule, d_plan, d_x0, d_desired, d_score, B, n, S, b0, d_out_plan, d_info);
+  call.adapt = adapt != nullptr;
+  if (adapt) {
+    for (int a = 0; a < 4; ++a) {
+      call.floor[a] = adapt->floor[a];
+      call.cap[a] = adapt->cap[a];
+    }
+    call.rate = adapt->rate;
+    for (int k = 0; k < 3; ++k) call.reserved[k] = adapt->reserved[k];
+  }
+  call.spread = d_spread;
+  call.out_spread = d_out_spread;
+  bool length = false;
+  if (const char *why = mppi_spread_refusal(call, &length)) return fail(length ? QILQR_ERR_LENGTH_MISMATCH : QILQR_ERR_INVALID_ARG, why);
+  HIP_TRY(hipSetDevice(s->device));
+  MppiSpreadLaunch go{};
+  if (int rc = mppi_launch_of(s, rule, seed, d_plan, d_x0, d_desired, d_score, B, n, S, b0, d_out_plan, d_info, go.base)) return rc;
+  go.d_spread = d_spread;
+  go.d_out_spread = d_out_spread;
+  if (adapting) {
+    for (int a = 0; a < 4; ++a) {
+      go.floor[a] = adapt->floor[a];
+      go.cap[a] = adapt->cap[a];
+    }
+    go.rate = adapt->rate;
+  }
+  // (enqueued on the handle's stream; not waited for)
+  const hipError_t e = adapting ? launch_mppi_adapt(s->stream, s->consts, go) : launch_mppi_flight_spread(s->stream, s->consts, go);
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string(adapting ? "k_mppi_adapt: " : "k_mppi_flight_spread: ") + hipGetErrorString(e));
   return QILQR_OK;
 }
 }  // namespace
@@ -368,5 +418,16 @@ int qilqr_mppi_update_device(qilqr_solver *s, const qilqr_mppi_rule *rule, uint6
                              const double *d_desired, const double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_out_plan,
                              double *d_info) {
   return mppi_device(s, true, rule, seed, d_plan, d_x0, d_desired, const_cast<double *>(d_score), B, n, S, b0, d_out_plan, d_info);
+}
+static_assert(sizeof(qilqr_mppi_adapt_rule) == 96, "mppi_adapt_launch.h and the C header agree on the adapt rule");
+int qilqr_mppi_flight_spread_device(qilqr_solver *s, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0,
+                                    const double *d_desired, const double *d_spread, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_score) {
+  return mppi_spread_device(s, false, rule, nullptr, seed, d_plan, d_x0, d_desired, d_spread, d_score, B, n, S, b0, nullptr, nullptr, nullptr);
+}
+int qilqr_mppi_adapt_device(qilqr_solver *s, const qilqr_mppi_rule *rule, const qilqr_mppi_adapt_rule *adapt, uint64_t seed, const double *d_plan,
+                            const double *d_x0, const double *d_desired, const double *d_spread, const double *d_score, int32_t B, int32_t n, int32_t S,
+                            int32_t b0, double *d_out_plan, double *d_out_spread, double *d_info) {
+  return mppi_spread_device(s, true, rule, adapt, seed, d_plan, d_x0, d_desired, d_spread, const_cast<double *>(d_score), B, n, S, b0, d_out_plan,
+                            d_out_spread, d_info);
 }
 }  // extern "C"

@@ -36,6 +36,7 @@
 #include "monte_carlo_launch.h"
 #include "risk_launch.h"
 #include "mppi_launch.h"
+#include "mppi_adapt_launch.h"
 
 using namespace qilqr;
 

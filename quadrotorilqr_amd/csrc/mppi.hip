@@ -1,7 +1,8 @@
 // mppi.hip -- the translation unit of k_mppi_flight and k_mppi_update (mppi_kernels.h), the device side of qilqr_mppi_flight_device and
 // qilqr_mppi_update_device.  A unit beside closed_loop_scored.hip and monte_carlo.hip, whose kernels stay what they were: the eight
-// instantiations of the flight are {Euler, Runge-Kutta} x the four of launch_ext.h, the update's five are its block sizes.  Exports two
-// hidden functions (mppi_launch.h), which host/caller_arrays.h calls.
+// instantiations of the flight are {Euler, Runge-Kutta} x the four of launch_ext.h, the update's five are its block sizes.  Exports three
+// hidden functions (mppi_launch.h): two that host/caller_arrays.h calls, and the nominal flight behind an update, which mppi_adapt.hip
+// enqueues behind its own.
 #include <hip/hip_runtime.h>
 
 #include "mppi_kernels.h"
@@ -25,29 +26,7 @@ hipError_t flight(hipStream_t stream, const ModelConsts<double> &c, const MppiLa
                   bool nominal, double *traj) {
   const long blocks = mppi_flight_blocks(call.B, S);
   if (blocks <= 0) return hipErrorInvalidValue;
-  MppiFlightArgs a{};
-  a.plan = plan;
-  a.x0 = call.d_x0 ? call.d_x0 : call.d_plan + 1;
-  a.x0_step = call.d_x0 ? CL_STATE : 18l * call.n;
-  a.desired = call.d_desired;
-  a.desired_step = call.desired_step;
-  a.q = call.d_q;
-  a.q_step = call.q_step;
-  a.shared = call.d_shared;
-  a.n_shared = call.n_shared;
-  a.own = call.d_own;
-  a.own_counts = call.d_own_counts;
-  a.own_K = call.own_K;
-  a.score = score;
-  a.score_step = score_step;
-  a.traj = traj;
-  a.B = call.B;
-  a.n = call.n;
-  a.S = S;
-  a.b0 = (uint32_t)call.b0;
-  a.flags = call.flags;
-  a.all_nominal = nominal ? 1 : 0;
-  a.seed = call.seed;
+  MppiFlightArgs a = mppi_flight_args(call, plan, S, score, score_step, nominal, traj);
   mppi_coeffs(call.sigma, call.tau_s, c.dt, a.m);
   return call.integrator == 1 ? flight_go<1>(stream, c, a, dim3((unsigned)blocks), call) : flight_go<0>(stream, c, a, dim3((unsigned)blocks), call);
 }
@@ -91,7 +70,11 @@ hipError_t launch_mppi_update(hipStream_t stream, const ModelConsts<double> &con
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  // the new plan's own flight: its states from x0 over d_out_plan, its score into words 4 .. 7 of d_info
+  return launch_mppi_nominal_flight(stream, consts, call);
+}
+
+// the new plan's own flight: its states from x0 over d_out_plan, its score into words 4 .. 7 of d_info
+hipError_t launch_mppi_nominal_flight(hipStream_t stream, const ModelConsts<double> &consts, const MppiLaunch &call) {
   return flight(stream, consts, call, call.d_out_plan, 1, call.d_info + 4, MPPI_INFO, true, call.d_out_plan);
 }
 

@@ -198,6 +198,13 @@ struct MppiSample {
   double *traj;           // its first knot, or null: no trajectory store is issued
 };
 
+// A fetch that says so here also gives the knot's deviations: the recursion is then the UNIT one and the fetch's eps(i, z, nominal, e)
+// makes the perturbation of it (mppi_adapt_kernels.h: e = spread_i z, a rounded product).  The fetches of this file do not.
+template <typename Fetch>
+struct MppiFetchSpreads {
+  static constexpr bool value = false;
+};
+
 // One sample: closed_loop_sample<.., SCORE> (closed_loop_kernels.h) with the law u = plan_u + K dx replaced by u = plan_u + eps_i, the
 // state started at knot 0 and no statistics.  The clamp, the trajectory store, the score of a knot (the same knot_cost instantiation,
 // cl_score_spheres, the same running minimum and count) and the step are that routine's, statement for statement.
@@ -221,8 +228,15 @@ QILQR_HD void mppi_sample(const ModelConsts<double> &c, const MppiCoeffs &m, Fet
     fetch(i, pt);
     mppi_eps_row(m, s.seed, s.plan, s.sample, (uint32_t)i, s.nominal, g);
     double u[4];
+    if constexpr (MppiFetchSpreads<Fetch>::value) {
+      double e[4];
+      fetch.eps(i, g, s.nominal, e);
 #pragma unroll
-    for (int a = 0; a < 4; ++a) u[a] = pt[14 + a] + g[a];
+      for (int a = 0; a < 4; ++a) u[a] = pt[14 + a] + e[a];
+    } else {
+#pragma unroll
+      for (int a = 0; a < 4; ++a) u[a] = pt[14 + a] + g[a];
+    }
     if (LIM) {
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
@@ -292,6 +306,35 @@ struct MppiFlightArgs {
   uint64_t seed;
   MppiCoeffs m;
 };
+// (host) the arguments of a flight of S samples per plan over `plan` from a launch record with MppiLaunch's fields (mppi_launch.h); the
+// coefficients are the caller's to fill
+template <typename Launch>
+inline MppiFlightArgs mppi_flight_args(const Launch &call, const double *plan, int S, double *score, long score_step, bool nominal, double *traj) {
+  MppiFlightArgs a{};
+  a.plan = plan;
+  a.x0 = call.d_x0 ? call.d_x0 : call.d_plan + 1;
+  a.x0_step = call.d_x0 ? CL_STATE : 18l * call.n;
+  a.desired = call.d_desired;
+  a.desired_step = call.desired_step;
+  a.q = call.d_q;
+  a.q_step = call.q_step;
+  a.shared = call.d_shared;
+  a.n_shared = call.n_shared;
+  a.own = call.d_own;
+  a.own_counts = call.d_own_counts;
+  a.own_K = call.own_K;
+  a.score = score;
+  a.score_step = score_step;
+  a.traj = traj;
+  a.B = call.B;
+  a.n = call.n;
+  a.S = S;
+  a.b0 = (uint32_t)call.b0;
+  a.flags = call.flags;
+  a.all_nominal = nominal ? 1 : 0;
+  a.seed = call.seed;
+  return a;
+}
 
 // the LDS image of a block: what is the same for the 64 samples of a plan, read by every lane at one address (a broadcast: no bank conflict)
 //     knot[2][18]   the plan knot (9 pairs) and the desired knot (9), double-buffered: loaded two knots ahead by lanes 0 .. 17 into a

@@ -143,6 +143,8 @@ struct MppiLaunch {
 // k_mppi_update, then k_mppi_flight with one sample, eps = 0 and the trajectory store on, over d_out_plan.
 __attribute__((visibility("hidden"))) hipError_t launch_mppi_flight(hipStream_t stream, const ModelConsts<double> &consts, const MppiLaunch &call);
 __attribute__((visibility("hidden"))) hipError_t launch_mppi_update(hipStream_t stream, const ModelConsts<double> &consts, const MppiLaunch &call);
+// the second launch alone (mppi_adapt.hip enqueues it behind k_mppi_adapt): reads d_plan (knot 0, without d_x0), d_out_plan and writes it, and words 4 .. 7 of d_info
+__attribute__((visibility("hidden"))) hipError_t launch_mppi_nominal_flight(hipStream_t stream, const ModelConsts<double> &consts, const MppiLaunch &call);
 
 }  // namespace qilqr
 #endif

@@ -14,7 +14,9 @@ Between two ticks the plan can be flown closed loop: tick(x0, gains=True) also l
 (closed_loop_device with one sample per plan and i0 = i1 = i); evaluate(x0, wrench) flies S sampled states per plan under that law -- and
 under sampled disturbances -- and returns the statistics and the score of every flight (closed_loop_device with out_score), on device
 buffers.  Ahead of a solve, start / tick(..., explore=dict(S=, seed=, sigma=, lambda_=)) runs rounds of the sampling planner on the
-shifted plan (mppi_flight_device, mppi_update_device): the solve then polishes what the samples found.
+shifted plan (mppi_flight_device, mppi_update_device): the solve then polishes what the samples found.  With one more key,
+adapt=dict(rate=, floor=, cap=), the planner's spread is kept per plan, knot and rotor in `self.spread` (B, n, 4), adapted by every round
+(mppi_flight_spread_device, mppi_adapt_device) and shifted along the horizon with the plan.
 """
 import numpy as np
 
@@ -50,6 +52,9 @@ class RecedingHorizon:
         self._pad = None                 # evaluate_sampled()'s copies with padded candidates: (C, S, x_nom (C, V + 1, 13), x0 (C, V S + 1, 13) or None)
         self._sel = None                 # select()'s outputs for the last C: (C, choice, info, plan, gains)
         self._mppi = None                # _explore()'s buffers for the last S: (S, a scratch plan (B, n, 18), score (B, S, 4), info (B, 8))
+        self.spread = None               # the planner's spread (B, n, 4) while explore carries `adapt`: what the last round left
+        self._spread_scratch = None      # ... and the buffer the next round writes
+        self._held = None                # the shifted spread of a tick that was refused
 
     def _to_device(self, a, dst):
         import torch
@@ -84,27 +89,51 @@ class RecedingHorizon:
             res["gains"] = self.gains
         return res
 
-    def _explore(self, explore):
+    def _explore(self, explore, steps=None):
         """`iterations` rounds of the sampling planner on the plan in the current buffer, before its solve: S control-perturbed flights
         from the plan's knot 0 (QuadrotorILQRBatch.mppi_flight_device) and the plan moved to their weighted mean (mppi_update_device),
         out of the current buffer into a scratch buffer, which then becomes the current one.  Enqueued on the solver's stream, behind
-        torch's current stream, and not waited for: the solve that follows is ordered behind it.  Returns the last round's info (B, 8)."""
+        torch's current stream, and not waited for: the solve that follows is ordered behind it.  Returns the last round's info (B, 8).
+        With explore["adapt"] a round is mppi_flight_spread_device and mppi_adapt_device over `self.spread`, which the round replaces;
+        before the first round the spread is set to sigma (steps None: a start) or shifted `steps` knots with a tail of sigma (a tick), by
+        torch on its current stream -- the first enqueue is ordered behind it."""
         import torch
-        known = {"S", "seed", "sigma", "lambda_", "tau_s", "collision_cost", "iterations", "first_is_nominal"}
+        known = {"S", "seed", "sigma", "lambda_", "tau_s", "collision_cost", "iterations", "first_is_nominal", "adapt"}
         if not isinstance(explore, dict) or not {"S", "seed", "sigma", "lambda_"} <= set(explore) or set(explore) - known:
-            raise TypeError("explore must be a dict with S, seed, sigma, lambda_ and optionally tau_s, collision_cost, iterations, first_is_nominal")
+            raise TypeError("explore must be a dict with S, seed, sigma, lambda_ and optionally tau_s, collision_cost, iterations, first_is_nominal, adapt")
         S, rounds = int(explore["S"]), int(explore.get("iterations", 1))
         if S <= 0 or rounds <= 0:
             raise TypeError("explore: S and iterations must be positive")
+        adapt = explore.get("adapt")
+        if adapt is not None and (not isinstance(adapt, dict) or set(adapt) != {"rate", "floor", "cap"}):
+            raise TypeError("explore: adapt must be a dict with rate, floor and cap")
         if self._mppi is None or self._mppi[0] != S:
             new = lambda *s: torch.zeros(s, dtype=torch.float64, device=self.device)
             self._mppi = (S, new(self.B, self.n, capi.KNOT), new(self.B, S, capi.CL_SCORE), new(self.B, capi.MPPI_INFO))
         _, scratch, d_score, d_info = self._mppi
         kw = dict(tau_s=explore.get("tau_s", 0.0), collision_cost=explore.get("collision_cost", 0.0), first_is_nominal=explore.get("first_is_nominal", True))
+        if adapt is None:
+            self.spread = None  # (a later adaptation starts from sigma again)
+        else:
+            sig = np.atleast_1d(np.asarray(explore["sigma"], dtype=np.float64))
+            if sig.shape not in ((1,), (4,)):
+                raise TypeError("sigma must have 1 or 4 words")
+            sig = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(sig, (4,)))).to(self.device)
+            k = self.n if steps is None or self.spread is None else min(int(steps), self.n)
+            # (a new tensor: the spread before this tick stays what it was, for a tick that is refused)
+            self.spread = torch.cat([self.spread[:, k:], sig.expand(self.B, k, 4)], dim=1).contiguous() if k < self.n else sig.expand(self.B, self.n, 4).contiguous()
+            if self._spread_scratch is None:
+                self._spread_scratch = torch.zeros((self.B, self.n, 4), dtype=torch.float64, device=self.device)
         for r in range(rounds):
             src, seed = self._buf[self._cur], int(explore["seed"]) + r  # (a round's draws are its own)
-            self.solver.mppi_flight_device(src, d_score, seed, explore["sigma"], explore["lambda_"], wait_current_stream=r == 0, **kw)
-            self.solver.mppi_update_device(src, d_score, scratch, d_info, seed, explore["sigma"], explore["lambda_"], wait_current_stream=False, **kw)
+            if adapt is None:
+                self.solver.mppi_flight_device(src, d_score, seed, explore["sigma"], explore["lambda_"], wait_current_stream=r == 0, **kw)
+                self.solver.mppi_update_device(src, d_score, scratch, d_info, seed, explore["sigma"], explore["lambda_"], wait_current_stream=False, **kw)
+            else:
+                self.solver.mppi_flight_spread_device(src, self.spread, d_score, seed, explore["sigma"], explore["lambda_"], wait_current_stream=r == 0, **kw)
+                self.solver.mppi_adapt_device(src, self.spread, d_score, scratch, self._spread_scratch, d_info, seed, explore["sigma"], explore["lambda_"],
+                                              adapt["floor"], adapt["cap"], adapt["rate"], wait_current_stream=False, **kw)
+                self.spread, self._spread_scratch = self._spread_scratch, self.spread
             self._buf[self._cur], scratch = scratch, src
             self._mppi = (S, scratch, d_score, d_info)
         return d_info
@@ -286,14 +315,16 @@ class RecedingHorizon:
         with S, seed, sigma, lambda_ and optionally tau_s, collision_cost, iterations (1) and first_is_nominal (True) -- between the shift
         and the solve `iterations` rounds of the sampling planner run on the solver's stream (_explore: round r with seed + r, S perturbed
         flights from knot 0 and the plan moved to their weighted mean, through a scratch buffer), the solve polishes what they found, and
-        the result carries "explore", the last round's info (B, 8; QuadrotorILQRBatch.mppi_update_device's words).  A tick that is refused -- steps or tail out of
+        the result carries "explore", the last round's info (B, 8; QuadrotorILQRBatch.mppi_update_device's words).  With the key adapt =
+        dict(rate=, floor=, cap=) the rounds adapt the spread per plan, knot and rotor (`self.spread`, (B, n, 4): set to sigma by start,
+        shifted `steps` knots with a tail of sigma by every tick; mppi_flight_spread_device and mppi_adapt_device).  A tick that is refused -- steps or tail out of
         range, or no window of n knots left behind the new start -- raises and leaves the object and the handle's start as they were."""
         steps = int(steps)
         x0 = None if x0 is None else self._to_device(x0, self._x0)
         # (refuses steps or a tail out of range before anything of this object or of the handle has changed; the buffer it writes holds the
         # plan before last, which nobody reads any more)
         self.solver.shift_device(self._buf[self._cur], self._buf[self._cur ^ 1], x0=x0, steps=steps, tail=tail)
-        had_k0, had_cur = self.k0, self._cur
+        had_k0, had_cur, had_spread = self.k0, self._cur, self.spread
         try:
             if advance:
                 self.solver.set_horizon_start(had_k0 + steps)
@@ -301,7 +332,7 @@ class RecedingHorizon:
             self._cur ^= 1
             if explore is None:
                 return self._solve(keep_init, gains)
-            info = self._explore(explore)
+            info = self._explore(explore, steps)
             res = self._solve(keep_init, gains)
             res["explore"] = info
             return res
@@ -309,5 +340,6 @@ class RecedingHorizon:
             # a refused start or solve (past the end of the mission no window of n knots is left) leaves the last plan, its buffer and the
             # start it was solved at in force
             self.solver.set_horizon_start(had_k0)
-            self.k0, self._cur = had_k0, had_cur
+            self._held = self.spread  # (a flight that was enqueued before the refusal may still read the shifted spread: it is kept, not freed)
+            self.k0, self._cur, self.spread = had_k0, had_cur, had_spread
             raise

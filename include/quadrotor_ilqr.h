@@ -704,6 +704,58 @@ int qilqr_mppi_adapt_device(qilqr_solver *s, const qilqr_mppi_rule *rule, const 
                             const double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_out_plan,
                             double *d_out_spread, double *d_info);
 
+/* Linear covariance analysis of a plan's closed loop on the device (extension): how far the flights of qilqr_closed_loop_scored_device
+ * stray from a plan under a gust model and an uncertain start, to first order and without a sample.  Device arrays only; sharded handles
+ * have no such call (use a shard's solver).
+ *
+ * About a dynamically consistent plan the deviation dx_i = x_i (-) plan_i (the solver's tangent order [rho, theta, dv, dw]) of the law
+ * u = u_i + K_i dx obeys dx_{i+1} = F_i dx_i + G_i w_i for plan b over knots i0 .. i1, with F_i = A_i + B_i K_i:
+ *   - A_i, B_i are the Jacobians of the handle's step (its integrator, qilqr_set_integrator) at plan[b, i], with the model of problem b
+ *     while per-problem models are set for B;
+ *   - K_i is words 4..51 of d_gains[b, i], as the closed loop reads them; d_gains == NULL is the open loop, F_i = A_i;
+ *   - w_i is the wrench {F world frame, tau body frame} held over the step, and G_i (12 x 6) the step's Jacobian with respect to it.
+ *     Explicit Euler, exact: rows 6..8, columns 0..2 are dt R(q_i)^T / mass; rows 9..11, columns 3..5 are dt I^-1; zero elsewhere.
+ *     Runge-Kutta: the six wrench columns carried through the four stages.
+ * With S_g = diag(sigma_c^2) of rule->gust and rho_c = tau > 0 ? exp(-dt / tau) : 0 (qilqr_sample_gusts_device's, on the host in double):
+ *     Sigma_{i0} = diag(state_sigma^2)     C_{i0} = 0 (12 x 6)     m_{i0} = 0
+ *     Sigma_{i+1} = F Sigma F^T + F C G^T + G C^T F^T + G S_g G^T
+ *     C_{i+1}     = (F C + G S_g) diag(rho)          (rho = 0: white noise, C stays 0)
+ *     m_{i+1}     = F m_i + G mean
+ * QILQR_COV_WRENCH_HELD (rule->flags) is the n_w = 1 case, one wrench per flight: rho = 1 in the C recursion.
+ * IGNORED: the thrust limits (the clamp is not linear), the state-weight schedule, the desired trajectory, and the horizon start (sphere
+ * j of the plan's own table stands at c + i dt v at knot i of the call, as the scored flight places it).
+ *
+ * Any output may be NULL, but not all of them.
+ *   d_cov      B x n x QILQR_COV: Sigma_i row-major for i0 <= i <= i1; other knots are left untouched.  Exactly symmetric: entry (k, l)
+ *              with k <= l is mirrored, so cov[k][l] and cov[l][k] have the same bits.
+ *   d_mean     B x n x 12: m_i, likewise.
+ *   d_summary  B x QILQR_COV_SUMMARY, with P_i = Sigma_i[0:3, 0:3]:
+ *     0  max_i sqrt(tr P_i), m                      4  the smallest z = (|d| - radius_j) / sqrt(n^T P_i n) over the knots and every
+ *     1  its knot, the first on ties                   sphere of both tables (the shared one first, then row b of the per-problem table):
+ *     2  sqrt(tr P_i1)                                 d = p_i + R_i m_i[0:3] - c_j(i), n = R_i^T d / |d| (the tangent's first three
+ *     3  max_i sqrt(tr Sigma_i[3:6, 3:6]), rad         words are body-frame); +inf without spheres; taken by z < best: never a NaN
+ *     7  max over i and rotor a of                  5  its knot (-1: none was taken)
+ *        sqrt(K_a Sigma_i K_a^T), N; 0 in the       6  its sphere: j, or shared_count + j for the plan's own table; -1: none
+ *        open loop
+ *
+ * ENQUEUES on the handle's stream (three launches: the knots' F and G, the chain over the knots, the summary) and does not drain it, with
+ * the ordering rules of qilqr_closed_loop_device; scratch the handle owns grows at the call that needs more.  QILQR_ERR_INVALID_ARG,
+ * before the device is touched, in this order: a NULL rule or d_plan; every output NULL; a non-positive B or n; knots not
+ * 0 <= i0 <= i1 <= n - 1; a negative or non-finite sigma or tau; a non-finite mean; unknown flag bits or reserved != 0; an array off a
+ * 16-byte boundary; an output overlapping an input or another output; a NULL handle, a mixed-precision one; per-problem models or
+ * per-problem spheres set for another B. */
+#define QILQR_COV 144
+#define QILQR_COV_SUMMARY 8
+#define QILQR_COV_WRENCH_HELD 1u
+typedef struct {
+  double state_sigma[12];  /* the deviations of the start state at knot i0 over the tangent [rho, theta, dv, dw] (qilqr_sample_states_device's sigma12) */
+  qilqr_gust_model gust;   /* mean, sigma and correlation times of the wrench */
+  uint32_t flags;          /* QILQR_COV_WRENCH_HELD, or 0 */
+  uint32_t reserved;       /* 0 */
+} qilqr_cov_rule;          /* 216 bytes */
+int qilqr_covariance_device(qilqr_solver *s, const qilqr_cov_rule *rule, const double *d_plan, const double *d_gains, int32_t B, int32_t n,
+                            int32_t i0, int32_t i1, double *d_cov, double *d_mean, double *d_summary);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -845,8 +897,8 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * qilqr_reduce_scores_device, qilqr_gust_model, QILQR_MC_SUMMARY, qilqr_risk_scores_device, qilqr_select_plans_device,
  * qilqr_select_rule, QILQR_MC_RISK, QILQR_RISK_MAX_LEVELS, QILQR_RISK_MAX_SAMPLES, QILQR_RISK_COST, QILQR_RISK_CLEARANCE,
  * QILQR_SELECT_INFO, qilqr_mppi_flight_device, qilqr_mppi_update_device, qilqr_mppi_rule, QILQR_MPPI_INFO,
- * QILQR_MPPI_FIRST_IS_NOMINAL, qilqr_mppi_flight_spread_device, qilqr_mppi_adapt_device and qilqr_mppi_adapt_rule were added within
- * version 7: no structure changed. */
+ * QILQR_MPPI_FIRST_IS_NOMINAL, qilqr_mppi_flight_spread_device, qilqr_mppi_adapt_device, qilqr_mppi_adapt_rule, qilqr_covariance_device,
+ * qilqr_cov_rule, QILQR_COV, QILQR_COV_SUMMARY and QILQR_COV_WRENCH_HELD were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

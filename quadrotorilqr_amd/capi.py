@@ -47,6 +47,9 @@ SELECT_INFO = 4  # QILQR_SELECT_INFO: the chosen objective, the number of feasib
 SELECT_OBJECTIVES = {"mean": 0, "worst": 1, "var": 2, "cvar": 3}  # qilqr_select_rule.objective: summary words 0 and 2, risk words 0 and 1
 MPPI_INFO = 8  # QILQR_MPPI_INFO: J_min, its sample, the effective sample size, the finite samples, the four score words of the new plan (mppi_update_device)
 MPPI_FIRST_IS_NOMINAL = 1  # QILQR_MPPI_FIRST_IS_NOMINAL: qilqr_mppi_rule.flags, sample 0 flies the plan's own controls
+COV = 144  # QILQR_COV: a knot's covariance, 12 x 12 row-major over the tangent [rho, theta, dv, dw] (covariance_device)
+COV_SUMMARY = 8  # QILQR_COV_SUMMARY: max sqrt(tr P), its knot, sqrt(tr P) at the last knot, max rotation deviation, smallest clearance z, its knot, its sphere, max control deviation
+COV_WRENCH_HELD = 1  # QILQR_COV_WRENCH_HELD: qilqr_cov_rule.flags, one wrench per flight
 CL_STATS = 4  # QILQR_CL_STATS: max position error, max rotation error, |dx| at the last knot, clamped (knot, rotor) pairs (closed_loop)
 
 # every symbol include/quadrotor_ilqr.h declares
@@ -63,6 +66,7 @@ EXPORTS = (
     "qilqr_sample_gusts_device", "qilqr_sample_states_device", "qilqr_reduce_scores_device",
     "qilqr_risk_scores_device", "qilqr_select_plans_device",
     "qilqr_mppi_flight_device", "qilqr_mppi_update_device", "qilqr_mppi_flight_spread_device", "qilqr_mppi_adapt_device",
+    "qilqr_covariance_device",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -106,6 +110,10 @@ class MppiRule(C.Structure):
 
 class MppiAdaptRule(C.Structure):
     _fields_ = [("floor", C.c_double * 4), ("cap", C.c_double * 4), ("rate", C.c_double), ("reserved", C.c_double * 3)]
+
+
+class CovRule(C.Structure):
+    _fields_ = [("state_sigma", C.c_double * 12), ("gust", GustModel), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Profile(C.Structure):
@@ -169,6 +177,7 @@ def load():
         lib.qilqr_mppi_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p] * 2
         lib.qilqr_mppi_flight_spread_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
         lib.qilqr_mppi_adapt_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 3
+        lib.qilqr_covariance_device.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p] * 3
         _lib = lib
     return _lib
 
@@ -358,6 +367,21 @@ def mppi_adapt_rule(floor, cap, rate):
             raise TypeError(f"{name} must have 1 or 4 words")
         return (C.c_double * 4)(*v)
     return MppiAdaptRule(four(floor, "floor"), four(cap, "cap"), float(rate), (C.c_double * 3)(0.0, 0.0, 0.0))
+
+
+def cov_rule(state_sigma, gust=None, wrench_held=False):
+    """a qilqr_cov_rule: state_sigma 12 words over the tangent [rho, theta, dv, dw] (or one number for all); gust None (no disturbance), a
+    GustModel, or a dict with the fields of gust_model (sigma, and optionally mean, tau_force_s, tau_torque_s); wrench_held: one wrench
+    per flight (QILQR_COV_WRENCH_HELD)"""
+    sig = np.atleast_1d(np.asarray(state_sigma, dtype=np.float64))
+    sig = np.repeat(sig, 12) if sig.shape == (1,) else sig
+    if sig.shape != (12,):
+        raise TypeError("state_sigma must have 1 or 12 words")
+    if gust is None:
+        gust = gust_model(0.0)
+    elif not isinstance(gust, GustModel):
+        gust = gust_model(**gust)
+    return CovRule((C.c_double * 12)(*sig), gust, COV_WRENCH_HELD if wrench_held else 0, 0)
 
 
 def _tail(tail):
@@ -929,6 +953,29 @@ class QuadrotorILQRBatch:
         vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
         _check(load().qilqr_mppi_adapt_device(self._h, C.byref(rule), C.byref(adapt), C.c_uint64(int(seed)), vp(plan), vp(x0), vp(desired), vp(spread),
                                               vp(score), C.c_int32(B), C.c_int32(n), C.c_int32(S), C.c_int32(int(b0)), vp(out_plan), vp(out_spread), vp(info)))
+
+    # ---- linear covariance analysis of a plan's closed loop: the first-order answer to what the Monte-Carlo loop samples
+    def covariance_device(self, plan, gains, state_sigma, gust=None, i0=0, i1=None, wrench_held=False, cov=None, mean=None, summary=None,
+                          wait_current_stream=True):
+        """qilqr_covariance_device on torch tensors: the covariance of the deviation dx_i = x_i (-) plan_i of the law u = u_i + K_i dx over
+        knots i0 .. i1 (i1 = None: n - 1) of plan (B, n, 18) with gains (B, n, 52), or None: the open loop -- from a start state with
+        deviations state_sigma (12 words over [rho, theta, dv, dw], or one number) under the gust model `gust` (cov_rule's forms), with the
+        handle's step and per-problem models.  Outputs, any but not all None: cov (B, n, 144), written at knots i0 .. i1 only; mean
+        (B, n, 12); summary (B, 8): max sqrt(tr P), its knot, sqrt(tr P) at i1, max rotation deviation, the smallest clearance to a sphere
+        of the handle's two tables in standard deviations, its knot, its sphere, the largest control deviation.  float64, contiguous, on
+        the solver's device.  ENQUEUED on the solver's own stream and not waited for, as closed_loop_device."""
+        if plan is None or plan.dim() != 3 or plan.shape[2] != KNOT:
+            raise TypeError("plan must be (B, n, 18)")
+        B, n = int(plan.shape[0]), int(plan.shape[1])
+        i1 = n - 1 if i1 is None else int(i1)
+        self._device_tensors(((plan, "plan", (B, n, KNOT)), (gains, "gains", (B, n, GAIN)), (cov, "cov", (B, n, COV)), (mean, "mean", (B, n, 12)),
+                              (summary, "summary", (B, COV_SUMMARY))))
+        rule = cov_rule(state_sigma, gust, wrench_held)
+        if wait_current_stream:
+            self._wait_current_stream(plan)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        _check(load().qilqr_covariance_device(self._h, C.byref(rule), vp(plan), vp(gains), C.c_int32(B), C.c_int32(n), C.c_int32(int(i0)), C.c_int32(i1),
+                                              vp(cov), vp(mean), vp(summary)))
 
     def profile_get(self):
         p = Profile()

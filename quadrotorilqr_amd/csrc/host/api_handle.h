@@ -175,6 +175,8 @@ void qilqr_destroy(qilqr_solver *s) {
   if (s->d_pobs_counts) (void)hipFree(s->d_pobs_counts);
   if (s->d_qsched) (void)hipFree(s->d_qsched);
   if (s->d_cl_q) (void)hipFree(s->d_cl_q);
+  if (s->d_cov_image) (void)hipFree(s->d_cov_image);
+  if (s->d_cov_out) (void)hipFree(s->d_cov_out);
   if (s->d_consts) (void)hipFree(s->d_consts);
   if (s->h_counters) (void)hipHostFree(s->h_counters);
   if (s->h_active) (void)hipHostFree(s->h_active);

@@ -1,7 +1,8 @@
 // host/caller_arrays.h -- the C ABI of the calls that work on the caller's own arrays and use no workspace, no BatchState and no route: the
 // receding-horizon shift (k_shift: shift.hip), the backward pass over device arrays, the closed-loop flights of a plan (k_closed_loop and
 // k_closed_loop_scored: closed_loop.hip, closed_loop_scored.hip), the ends of the Monte-Carlo loop (monte_carlo.hip) and the risk
-// measures and the choice among candidate plans behind it (risk.hip), and the sampling planner (mppi.hip, mppi_adapt.hip).  Each call has
+// measures and the choice among candidate plans behind it (risk.hip), the sampling planner (mppi.hip, mppi_adapt.hip) and the linear
+// covariance analysis of a plan's closed loop (cov.hip; its rule is cov_launch.h's, its scratch the handle's).  Each call has
 // one refusal (from the rules of ranges.h, closed_loop_launch.h, monte_carlo_launch.h, risk_launch.h, mppi_launch.h and mppi_adapt_launch.h), one enqueue, a device form that enqueues and
 // returns, and -- the shift and the flight -- a host form that stages the arrays through one DeviceScratch.  Part of ilqr_capi.hip's
 // translation unit.
@@ -429,5 +430,78 @@ int qilqr_mppi_adapt_device(qilqr_solver *s, const qilqr_mppi_rule *rule, const 
                             int32_t b0, double *d_out_plan, double *d_out_spread, double *d_info) {
   return mppi_spread_device(s, true, rule, adapt, seed, d_plan, d_x0, d_desired, d_spread, const_cast<double *>(d_score), B, n, S, b0, d_out_plan,
                             d_out_spread, d_info);
+}
+}  // extern "C"
+
+// ---- linear covariance analysis of a plan's closed loop: k_cov_build, k_cov_chain and k_cov_summary (cov_kernels.h, compiled by cov.hip)
+// on the caller's device arrays.  The rule is cov_launch.h's; the handle gives its stream, its step, its models, its sphere tables and
+// the scratch of the knots' operand images.
+namespace {
+// `words` doubles at *p (the handle's), grown when the call needs more: what runs on the stream may still read the old one
+int cov_scratch(qilqr_solver *s, double **p, size_t *have, size_t words, bool zeroed) {
+  if (*have >= words) return QILQR_OK;
+  if (*p) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipFree(*p));
+    *p = nullptr;
+    *have = 0;
+  }
+  HIP_TRY(hipMalloc((void **)p, sizeof(double) * words));
+  *have = words;
+  // (the image's pads -- rows 12..15, wrench columns 6 and 7 -- are never written again: a knot's image is COV_IMAGE words wherever it lies)
+  if (zeroed) HIP_TRY(hipMemsetAsync(*p, 0, sizeof(double) * words, s->stream));
+  return QILQR_OK;
+}
+}  // namespace
+
+extern "C" {
+static_assert(QILQR_COV == 144 && QILQR_COV_SUMMARY == 8 && QILQR_COV_WRENCH_HELD == 1u && sizeof(qilqr_cov_rule) == 216,
+              "cov_kernels.h, cov_launch.h and the C header agree on the words of a covariance, of a summary, the flag and the rule");
+int qilqr_covariance_device(qilqr_solver *s, const qilqr_cov_rule *rule, const double *d_plan, const double *d_gains, int32_t B, int32_t n, int32_t i0,
+                            int32_t i1, double *d_cov, double *d_mean, double *d_summary) {
+  CovCall call{};
+  call.rule = rule != nullptr;
+  if (rule) {
+    for (int k = 0; k < 12; ++k) call.state_sigma[k] = rule->state_sigma[k];
+    for (int k = 0; k < 6; ++k) {
+      call.mean[k] = rule->gust.mean[k];
+      call.sigma[k] = rule->gust.sigma[k];
+    }
+    call.tau_force_s = rule->gust.tau_force_s;
+    call.tau_torque_s = rule->gust.tau_torque_s;
+    call.flags = rule->flags;
+    call.reserved = rule->reserved;
+  }
+  call.plan = d_plan; call.gains = d_gains; call.cov = d_cov; call.mean_out = d_mean; call.summary = d_summary;
+  call.B = B; call.n = n; call.i0 = i0; call.i1 = i1;
+  call.handle = s != nullptr;
+  if (s) {
+    call.f32 = s->f32; call.modeled = s->modeled; call.models_B = s->models_B; call.pobs_B = s->pobs_B;
+  }
+  if (const char *why = cov_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t knots = (size_t)B * (size_t)n;
+  if (int rc = cov_scratch(s, &s->d_cov_image, &s->cov_image_words, knots * COV_IMAGE, true)) return rc;
+  CovLaunch go{};
+  go.d_plan = d_plan; go.d_gains = d_gains; go.d_image = s->d_cov_image;
+  go.d_cov = d_cov; go.d_mean = d_mean; go.d_summary = d_summary;
+  if (d_summary && (!d_cov || !d_mean)) {  // the summary reads Sigma_i and m_i where the chain left them
+    if (int rc = cov_scratch(s, &s->d_cov_out, &s->cov_out_words, knots * (QILQR_COV + 12), false)) return rc;
+    if (!d_cov) go.d_cov = s->d_cov_out;
+    if (!d_mean) go.d_mean = s->d_cov_out + knots * QILQR_COV;
+  }
+  go.B = B; go.n = n; go.i0 = i0; go.i1 = i1;
+  go.integrator = s->integrator;
+  go.d_models = s->modeled ? s->d_models : nullptr;
+  cov_coeffs(rule->state_sigma, rule->gust.mean, rule->gust.sigma, rule->gust.tau_force_s, rule->gust.tau_torque_s, (rule->flags & QILQR_COV_WRENCH_HELD) != 0,
+             s->consts.dt, go.k);
+  go.d_shared = s->n_obstacles > 0 ? s->d_obstacles : nullptr;
+  go.n_shared = s->n_obstacles;
+  go.d_own = s->pobs_B > 0 ? s->d_pobs : nullptr;
+  go.d_own_counts = s->pobs_B > 0 ? s->d_pobs_counts : nullptr;
+  go.own_K = s->pobs_K;
+  const hipError_t e = launch_covariance(s->stream, s->consts, go);  // (enqueued on the handle's stream; not waited for)
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_cov_chain: ") + hipGetErrorString(e));
+  return QILQR_OK;
 }
 }  // extern "C"

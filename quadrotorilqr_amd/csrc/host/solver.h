@@ -52,6 +52,10 @@ struct qilqr_solver {
   void *d_desired = nullptr;    // shared desired trajectory, storage precision
   void *d_ctab = nullptr;       // constant operand table of k_backward, storage precision
   double *d_cl_q = nullptr;     // the handle's Q on a 16-byte boundary (qilqr_closed_loop_scored without a schedule), allocated at the first scored call
+  double *d_cov_image = nullptr;  // qilqr_covariance_device's scratch: the knots' operand images (cov_launch.h: COV_IMAGE words each, pads zeroed once),
+  size_t cov_image_words = 0;     // ... grown at the call that needs more
+  double *d_cov_out = nullptr;    // ... and Sigma_i, m_i of a call that asks for the summary without one of them (156 words a knot)
+  size_t cov_out_words = 0;
   void *d_consts = nullptr;     // the model constants in device memory (k_linearize reads them where it uses them)
   bool f32 = false;             // mixed-precision mode (qilqr_device_config.precision == 1)
   int integrator = 0;           // 0 explicit Euler (the reference), 1 the Runge-Kutta extension (qilqr_set_integrator)

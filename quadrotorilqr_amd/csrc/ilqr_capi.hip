@@ -37,6 +37,7 @@
 #include "risk_launch.h"
 #include "mppi_launch.h"
 #include "mppi_adapt_launch.h"
+#include "cov_launch.h"
 
 using namespace qilqr;
 

@@ -45,6 +45,7 @@ class RecedingHorizon:
         self._have_gains = False
         self._xc = self._ctl = None      # control()'s states (B, 1, 13) and the knots it writes (B, 1, n, 18)
         self._eval = None                # evaluate()'s buffers for the last S: (S, n_w, x0, wrench, stats, score)
+        self._cov = None                 # evaluate_covariance()'s: [summary, cov or None]
         self._mc = None                  # evaluate_sampled()'s for the last (S, n_w): (S, n_w, x_nom, x0, wrench, stats, score, summary)
         self.sampled = None              # ... and what its last call sampled: (x0 (B, S, 13), wrench (B, S, n_w, 6) or None), its buffers
         self._risk = None                # evaluate_sampled()'s risk array (B, L, 4) for the last L
@@ -199,6 +200,26 @@ class RecedingHorizon:
         # (enqueued on the solver's stream and not waited for: torch's stream waits for it before anything reads the results)
         torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
         return dict(stats=d_stats, score=d_score)
+
+    def evaluate_covariance(self, state_sigma, gust=None, wrench_held=False, cov=False):
+        """Linear covariance analysis about the last plan and its gains over the whole horizon (QuadrotorILQRBatch.covariance_device): how
+        far flights of the law stray from the plan for start-state deviations state_sigma (12 words over [rho, theta, dv, dw], or one
+        number) under `gust` (None, or a dict with the fields of qilqr_gust_model, as evaluate_sampled takes it) -- the first-order answer
+        to what evaluate_sampled samples, from one enqueue.  Needs the gains of the last plan (start / tick with gains=True), as evaluate()
+        does.  Returns {"summary": (B, 8), "cov": (B, n, 12, 12) or None}: views of device tensors this object owns, complete on torch's
+        current stream."""
+        import torch
+        if not self._have_gains:
+            raise RuntimeError("evaluate_covariance() needs the gains of the last plan: call start() or tick() with gains=True")
+        if self._cov is None:
+            self._cov = [torch.zeros((self.B, capi.COV_SUMMARY), dtype=torch.float64, device=self.device), None]
+        if cov and self._cov[1] is None:
+            self._cov[1] = torch.zeros((self.B, self.n, capi.COV), dtype=torch.float64, device=self.device)
+        d_sum, d_cov = self._cov[0], self._cov[1] if cov else None
+        self.solver.covariance_device(self._buf[self._cur], self.gains, state_sigma, gust=gust, wrench_held=wrench_held, cov=d_cov, summary=d_sum)
+        # (enqueued on the solver's stream and not waited for: torch's stream waits for it before anything reads the results)
+        torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
+        return dict(summary=d_sum, cov=None if d_cov is None else d_cov.view(self.B, self.n, 12, 12))
 
     def evaluate_sampled(self, x, S, seed, state_sigma, gust=None, n_w=None, first_is_nominal=True, risk_levels=None, risk_column="cost", candidates=1):
         """The Monte-Carlo loop about the last plan without the host: S start states per plan sampled about the measured states x (B, 13;

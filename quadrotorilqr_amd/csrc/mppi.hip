@@ -1,6 +1,7 @@
 // mppi.hip -- the translation unit of k_mppi_flight and k_mppi_update (mppi_kernels.h), the device side of qilqr_mppi_flight_device and
 // qilqr_mppi_update_device.  A unit beside closed_loop_scored.hip and monte_carlo.hip, whose kernels stay what they were: the eight
-// instantiations of the flight are {Euler, Runge-Kutta} x the four of launch_ext.h, the update's five are its block sizes.  Exports three
+// instantiations of the flight are {Euler, Runge-Kutta} x the four of launch_ext.h, the update's five are its block sizes
+// (with_update_lanes, mppi_launch.h).  Exports three
 // hidden functions (mppi_launch.h): two that host/caller_arrays.h calls, and the nominal flight behind an update, which mppi_adapt.hip
 // enqueues behind its own.
 #include <hip/hip_runtime.h>
@@ -30,11 +31,6 @@ hipError_t flight(hipStream_t stream, const ModelConsts<double> &c, const MppiLa
   mppi_coeffs(call.sigma, call.tau_s, c.dt, a.m);
   return call.integrator == 1 ? flight_go<1>(stream, c, a, dim3((unsigned)blocks), call) : flight_go<0>(stream, c, a, dim3((unsigned)blocks), call);
 }
-
-template <int THREADS>
-void update_go(hipStream_t stream, int B, const MppiUpdateArgs &a) {
-  hipLaunchKernelGGL(k_mppi_update<THREADS>, dim3((unsigned)B), dim3(THREADS), 0, stream, a);
-}
 }  // namespace
 
 hipError_t launch_mppi_flight(hipStream_t stream, const ModelConsts<double> &consts, const MppiLaunch &call) {
@@ -43,31 +39,12 @@ hipError_t launch_mppi_flight(hipStream_t stream, const ModelConsts<double> &con
 
 hipError_t launch_mppi_update(hipStream_t stream, const ModelConsts<double> &consts, const MppiLaunch &call) {
   if (call.S > MPPI_MAX_SAMPLES) return hipErrorInvalidValue;
-  MppiUpdateArgs a{};
-  a.plan = call.d_plan;
-  a.score = call.d_score;
-  a.out_plan = call.d_out_plan;
-  a.info = call.d_info;
-  a.n = call.n;
-  a.S = call.S;
-  a.b0 = (uint32_t)call.b0;
-  a.flags = call.flags;
-  a.seed = call.seed;
-  a.lambda = call.lambda;
-  a.collision_cost = call.collision_cost;
-  mppi_coeffs(call.sigma, call.tau_s, consts.dt, a.m);
-  a.limited = call.limits ? 1 : 0;
-  for (int r = 0; r < 4; ++r) {
-    a.lim_lo[r] = call.limits ? call.limits->lo[r] : 0.0;
-    a.lim_hi[r] = call.limits ? call.limits->hi[r] : 0.0;
-  }
-  switch (mppi_update_threads(call.S)) {
-    case 64: update_go<64>(stream, call.B, a); break;
-    case 128: update_go<128>(stream, call.B, a); break;
-    case 256: update_go<256>(stream, call.B, a); break;
-    case 512: update_go<512>(stream, call.B, a); break;
-    default: update_go<1024>(stream, call.B, a); break;
-  }
+  MppiCoeffs m;
+  mppi_coeffs(call.sigma, call.tau_s, consts.dt, m);
+  const MppiUpdateArgs a = mppi_update_args(call, m);
+  with_update_lanes(call.S, [&](auto lanes) {
+    hipLaunchKernelGGL(k_mppi_update<decltype(lanes)::value>, dim3((unsigned)call.B), dim3(decltype(lanes)::value), 0, stream, a);
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return launch_mppi_nominal_flight(stream, consts, call);

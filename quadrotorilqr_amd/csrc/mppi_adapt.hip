@@ -1,7 +1,8 @@
 // mppi_adapt.hip -- the translation unit of k_mppi_flight_spread and k_mppi_adapt (mppi_adapt_kernels.h), the device side of
 // qilqr_mppi_flight_spread_device and qilqr_mppi_adapt_device.  A unit beside mppi.hip, whose kernels stay what they were: the eight
 // instantiations of the flight are {Euler, Runge-Kutta} x the four of launch_ext.h, the adaptation's five are its block sizes.  Exports
-// two hidden functions (mppi_adapt_launch.h), which host/caller_arrays.h calls; the nominal flight behind the adaptation is mppi.hip's.
+// two hidden functions (mppi_adapt_launch.h), which host/caller_arrays.h calls; the nominal flight behind the adaptation is mppi.hip's,
+// and the common arguments and the block size are filled and chosen as there (mppi_flight_args, mppi_update_args, with_update_lanes).
 #include <hip/hip_runtime.h>
 
 #include "mppi_adapt_kernels.h"
@@ -17,11 +18,6 @@ hipError_t flight_go(hipStream_t stream, const ModelConsts<double> &c, const Mpp
     hipLaunchKernelGGL((k_mppi_flight_spread<INTEG, decltype(lim)...>), grid, dim3(CL_BLOCK), 0, stream, c, a, lim...);
     return hipGetLastError();
   });
-}
-
-template <int THREADS>
-void adapt_go(hipStream_t stream, int B, const MppiAdaptArgs &a) {
-  hipLaunchKernelGGL(k_mppi_adapt<THREADS>, dim3((unsigned)B), dim3(THREADS), 0, stream, a);
 }
 }  // namespace
 
@@ -40,33 +36,15 @@ hipError_t launch_mppi_adapt(hipStream_t stream, const ModelConsts<double> &cons
   const MppiLaunch &m = call.base;
   if (m.S > MPPI_MAX_SAMPLES) return hipErrorInvalidValue;
   MppiAdaptArgs a{};
-  a.u.plan = m.d_plan;
-  a.u.score = m.d_score;
-  a.u.out_plan = m.d_out_plan;
-  a.u.info = m.d_info;
-  a.u.n = m.n;
-  a.u.S = m.S;
-  a.u.b0 = (uint32_t)m.b0;
-  a.u.flags = m.flags;
-  a.u.seed = m.seed;
-  a.u.lambda = m.lambda;
-  a.u.collision_cost = m.collision_cost;
-  mppi_unit_coeffs(m.tau_s, consts.dt, a.u.m);
-  a.u.limited = m.limits ? 1 : 0;
-  for (int r = 0; r < 4; ++r) {
-    a.u.lim_lo[r] = m.limits ? m.limits->lo[r] : 0.0;
-    a.u.lim_hi[r] = m.limits ? m.limits->hi[r] : 0.0;
-  }
+  MppiCoeffs unit;
+  mppi_unit_coeffs(m.tau_s, consts.dt, unit);
+  a.u = mppi_update_args(m, unit);
   a.spread = call.d_spread;
   a.out_spread = call.d_out_spread;
   mppi_adapt_coeffs(call.floor, call.cap, call.rate, a.k);
-  switch (mppi_update_threads(m.S)) {
-    case 64: adapt_go<64>(stream, m.B, a); break;
-    case 128: adapt_go<128>(stream, m.B, a); break;
-    case 256: adapt_go<256>(stream, m.B, a); break;
-    case 512: adapt_go<512>(stream, m.B, a); break;
-    default: adapt_go<1024>(stream, m.B, a); break;
-  }
+  with_update_lanes(m.S, [&](auto lanes) {
+    hipLaunchKernelGGL(k_mppi_adapt<decltype(lanes)::value>, dim3((unsigned)m.B), dim3(decltype(lanes)::value), 0, stream, a);
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // the new plan's own flight: its states from x0 over d_out_plan, its score into words 4 .. 7 of d_info

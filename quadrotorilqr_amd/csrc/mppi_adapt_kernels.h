@@ -3,7 +3,8 @@
 //                          spread[B][n][4] instead of the rule's sigma
 //   k_mppi_adapt           k_mppi_update with the weighted SECOND moment of the perturbations beside the first: out_plan as the update
 //                          makes it, and out_spread[B][n][4], the spread blended towards the weighted deviation
-// and mppi.hip's nominal flight behind the second, as behind the update.
+// and mppi.hip's nominal flight behind the second, as behind the update.  The first is mppi_flight_block (mppi_kernels.h) over an LDS
+// image and a fetch with the deviations; the second repeats k_mppi_update's head statement for statement and has its own knot loop.
 //
 // THE PERTURBATION of sample j at knot i, rotor a:  eps_i[a] = spread[b, i, a] * z_i[a], a rounded product, where z is mppi_eps_row's
 // recursion with the coefficients of sigma = {1, 1, 1, 1} (mppi_unit_coeffs): z_0 = xi_0, z_i = fma(rho, z_{i-1}, kappa1 xi_i).  The
@@ -142,49 +143,14 @@ struct MppiFetchSpreads<MppiSharedSpreadFetch> {
   static constexpr bool value = true;
 };
 
-// k_mppi_flight's form and grid, word for word: a block is one wavefront of 64 samples of ONE plan, B cdiv(S, 64) blocks; lanes past S
-// fly a copy of sample S - 1 and store nothing.
+// k_mppi_flight's block (mppi_flight_block) over the base of this kernel's image, its fetch wrapped in MppiSharedSpreadFetch with plan b's
+// deviations; no trajectory store.
 template <int INTEG, typename... Lim>
 __global__ __launch_bounds__(CL_BLOCK) void k_mppi_flight_spread(ModelConsts<double> c, MppiFlightSpreadArgs as, Lim... lim) {
-  constexpr bool LIM = pack_has<ControlLimits, Lim...>;
-  constexpr bool MOD = pack_has<BatchModels, Lim...>;
-  const MppiFlightArgs &a = as.f;
-  const int lane = threadIdx.x;
-  const int per = (a.S + CL_BLOCK - 1) / CL_BLOCK;
-  const int b = (int)blockIdx.x / per;  // (block-uniform; the host launches exactly B * per blocks)
-  int j = ((int)blockIdx.x - b * per) * CL_BLOCK + lane;
-  const bool live = j < a.S;
-  if (!live) j = a.S - 1;
-  const double *lo = nullptr, *hi = nullptr;
-  if constexpr (LIM) {
-    const ControlLimits &L = pack_get<ControlLimits>(lim...);
-    lo = L.lo;
-    hi = L.hi;
-  }
-  const double *plan = a.plan + (long)b * a.n * 18, *desired = a.desired + (long)b * a.desired_step;
-  const int n_own = a.own ? a.own_counts[b] : 0;
   __shared__ MppiSpreadImage image;
-  MppiSample s;
-  s.x0 = a.x0 + (long)b * a.x0_step;
-  s.n = a.n;
-  s.seed = a.seed;
-  s.plan = a.b0 + (uint32_t)b;
-  s.sample = (uint32_t)j;
-  s.nominal = a.all_nominal != 0 || mppi_is_nominal(a.flags, j);
-  s.spheres = ClSpheres{image.base.shared, a.n_shared, image.base.own, n_own, 1, OB_BWORDS};
-  s.score = live ? a.score + (long)b * a.score_step + 4 * (long)j : nullptr;
-  s.traj = nullptr;
-  MppiSharedSpreadFetch fetch{
-      MppiSharedFetch{reinterpret_cast<const cl_dv2 *>(plan), reinterpret_cast<const cl_dv2 *>(desired), reinterpret_cast<const cl_dv2 *>(a.q), a.q_step / 2,
-                      &image.base, lane, a.n - 1, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}},
-      reinterpret_cast<const cl_dv2 *>(as.spread + 4 * (long)b * a.n), &image, cl_dv2{0.0, 0.0}};
-  fetch.prime(a.shared, a.n_shared, a.own, a.own_K, b, n_own);
-  if constexpr (MOD) {
-    const ModelConsts<double> cm = problem_model(c, pack_get<BatchModels>(lim...), (long)b);
-    mppi_sample<INTEG, LIM>(cm, a.m, fetch, s, lo, hi);
-  } else {
-    mppi_sample<INTEG, LIM>(c, a.m, fetch, s, lo, hi);
-  }
+  mppi_flight_block<INTEG, false>(c, as.f, image.base, [&](const MppiSharedFetch &base, int b) {
+    return MppiSharedSpreadFetch{base, reinterpret_cast<const cl_dv2 *>(as.spread + 4 * (long)b * as.f.n), &image, cl_dv2{0.0, 0.0}};
+  }, lim...);
 }
 
 #if defined(__clang__)
@@ -227,7 +193,7 @@ struct MppiAdaptArgs {
   MppiAdaptCoeffs k;
 };
 
-// k_mppi_update's form and grid, statement for statement up to the weighted perturbations: one block of THREADS = mppi_update_threads(S)
+// k_mppi_update's form and grid, statement for statement up to the weighted perturbations: one block of THREADS = mppi_update_lanes(S)
 // lanes per plan.  Then four more accumulators a lane, part2 beside part, the knot's deviations read by every lane at one address (from LDS,
 // a chunk's rows at a time), and out_spread written where the controls are.
 template <int THREADS>

@@ -6,6 +6,9 @@
 // and k_mppi_flight once more, with one sample, eps = 0 and its trajectory store on, fills the new plan's states and scores it.
 // No perturbation ever lies in memory: eps is a function of (seed, b0 + b, j, i) alone (philox.h, stream MC_STREAM_CONTROLS), drawn in
 // registers by the flight and REDRAWN by the update.
+// mppi_flight_block, the block of a flight kernel, is written here once for k_mppi_flight and for k_mppi_flight_spread of
+// mppi_adapt_kernels.h; mppi_flight_args and mppi_update_args fill the kernels' arguments for both units.  (k_mppi_adapt still repeats
+// k_mppi_update's head: with one shared routine for it the update measured 0.1 to 0.2 % slower at 64 x 1024 x 100 -- DESIGN.md section 8p.)
 //
 // The per-lane routines are QILQR_HD and carry all the arithmetic; tests/host_mppi_harness.cpp runs the same text on the host.
 //
@@ -14,7 +17,7 @@
 // with rho = tau_s > 0 ? exp(-dt / tau_s) : 0 and kappa_a = sigma_a sqrt((1 - rho)(1 + rho)) made once on the host (mppi_coeffs), and xi
 // normal a % 2 of mc_draw(seed, b0 + b, j, i, MC_STREAM_CONTROLS, a / 2).  With MPPI_FIRST_IS_NOMINAL sample 0 has eps = 0 at every knot.
 //
-// THE UPDATE of plan b, in this order (one block of T = mppi_update_threads(S) lanes -- a function of S alone; "lane" t is thread t of the block):
+// THE UPDATE of plan b, in this order (one block of T = mppi_update_lanes(S) lanes, mppi_launch.h -- a function of S alone; "lane" t is thread t of the block):
 //     J_j   = cost_j, or cost_j + collision_cost hits_j where hits_j > 0              (mppi_key; a key that is not finite: weight 0)
 //     J_min = the smallest finite key, the smaller j on ties; n_f the finite keys     (exact: comparisons and integer sums)
 //     w_j   = exp(-(J_j - J_min) / lambda)                                             (mppi_weight)
@@ -46,14 +49,6 @@ constexpr int MPPI_KNOT_PAIRS = 2 * MPPI_PLAN_PAIRS;
 constexpr int MPPI_UPDATE_MAX_THREADS = 1024;
 constexpr int MPPI_PER_LANE = MPPI_MAX_SAMPLES / MPPI_UPDATE_MAX_THREADS;  // samples a lane of the update carries at most: 4
 constexpr int MPPI_CHUNK = 8;                    // knots between two block-wide combinations of the update
-
-// the lanes of the update's block: the power of two >= S, a wavefront at the least and 1024 at the most (a lane without a sample
-// folds nothing and adds +0 to the sums)
-QILQR_HD int mppi_update_threads(int S) {
-  int T = 64;
-  while (T < S && T < MPPI_UPDATE_MAX_THREADS) T <<= 1;
-  return T;
-}
 
 // what the host makes of a qilqr_mppi_rule and the handle's dt
 struct MppiCoeffs {
@@ -406,11 +401,14 @@ struct MppiSharedFetch {
   }
 };
 
-// One form: a block is one wavefront of 64 samples of ONE plan; grid B cdiv(S, 64), block g of plan g / cdiv(S, 64).  Lanes past S fly a
-// copy of sample S - 1 (they take part in the loads and the barriers) and store nothing.  Lim as k_closed_loop takes it: ControlLimits,
-// BatchModels (plan b steps with model b), both (ControlLimits first) or neither.
-template <int INTEG, typename... Lim>
-__global__ __launch_bounds__(CL_BLOCK) void k_mppi_flight(ModelConsts<double> c, MppiFlightArgs a, Lim... lim) {
+// The block of both flight kernels (k_mppi_flight here, k_mppi_flight_spread of mppi_adapt_kernels.h), written once: a block is one
+// wavefront of 64 samples of ONE plan; grid B cdiv(S, 64), block g of plan g / cdiv(S, 64).  Lanes past S fly a copy of sample S - 1 (they
+// take part in the loads and the barriers) and store nothing.  `image` is the block's MppiImage, and wrap(base, b) makes the kernel's
+// fetch of the MppiSharedFetch over it for plan b.  TRAJ: the kernel has a trajectory store (sample 0's flight over a.traj, where that is
+// given); without it no store is compiled.  The arguments come BY VALUE, as a kernel's own do: handed over by reference the sixteen
+// kernels are allocated registers differently and the eight of k_mppi_flight change length, by value each keeps its instructions.
+template <int INTEG, bool TRAJ, typename Wrap, typename... Lim>
+__device__ __forceinline__ void mppi_flight_block(const ModelConsts<double> &c, const MppiFlightArgs a, MppiImage &image, Wrap wrap, Lim... lim) {
   constexpr bool LIM = pack_has<ControlLimits, Lim...>;
   constexpr bool MOD = pack_has<BatchModels, Lim...>;
   const int lane = threadIdx.x;
@@ -427,7 +425,6 @@ __global__ __launch_bounds__(CL_BLOCK) void k_mppi_flight(ModelConsts<double> c,
   }
   const double *plan = a.plan + (long)b * a.n * 18, *desired = a.desired + (long)b * a.desired_step;
   const int n_own = a.own ? a.own_counts[b] : 0;
-  __shared__ MppiImage image;
   MppiSample s;
   s.x0 = a.x0 + (long)b * a.x0_step;
   s.n = a.n;
@@ -437,9 +434,10 @@ __global__ __launch_bounds__(CL_BLOCK) void k_mppi_flight(ModelConsts<double> c,
   s.nominal = a.all_nominal != 0 || mppi_is_nominal(a.flags, j);
   s.spheres = ClSpheres{image.shared, a.n_shared, image.own, n_own, 1, OB_BWORDS};
   s.score = live ? a.score + (long)b * a.score_step + 4 * (long)j : nullptr;
-  s.traj = (live && j == 0 && a.traj) ? a.traj + (long)b * a.n * 18 : nullptr;
-  MppiSharedFetch fetch{reinterpret_cast<const cl_dv2 *>(plan), reinterpret_cast<const cl_dv2 *>(desired), reinterpret_cast<const cl_dv2 *>(a.q),
-                        a.q_step / 2, &image, lane, a.n - 1, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}};
+  s.traj = (TRAJ && live && j == 0 && a.traj) ? a.traj + (long)b * a.n * 18 : nullptr;
+  auto fetch = wrap(MppiSharedFetch{reinterpret_cast<const cl_dv2 *>(plan), reinterpret_cast<const cl_dv2 *>(desired), reinterpret_cast<const cl_dv2 *>(a.q),
+                                    a.q_step / 2, &image, lane, a.n - 1, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}},
+                    b);
   fetch.prime(a.shared, a.n_shared, a.own, a.own_K, b, n_own);
   if constexpr (MOD) {
     const ModelConsts<double> cm = problem_model(c, pack_get<BatchModels>(lim...), (long)b);
@@ -447,6 +445,13 @@ __global__ __launch_bounds__(CL_BLOCK) void k_mppi_flight(ModelConsts<double> c,
   } else {
     mppi_sample<INTEG, LIM>(c, a.m, fetch, s, lo, hi);
   }
+}
+
+// Lim as k_closed_loop takes it: ControlLimits, BatchModels (plan b steps with model b), both (ControlLimits first) or neither.
+template <int INTEG, typename... Lim>
+__global__ __launch_bounds__(CL_BLOCK) void k_mppi_flight(ModelConsts<double> c, MppiFlightArgs a, Lim... lim) {
+  __shared__ MppiImage image;
+  mppi_flight_block<INTEG, true>(c, a, image, [](const MppiSharedFetch &base, int) { return base; }, lim...);
 }
 
 #if defined(__clang__)
@@ -467,6 +472,30 @@ struct MppiUpdateArgs {
   double lim_lo[4], lim_hi[4];
 };
 
+// (host) the arguments of an update from a launch record with MppiLaunch's fields (mppi_launch.h) and the recursion's coefficients
+template <typename Launch>
+inline MppiUpdateArgs mppi_update_args(const Launch &call, const MppiCoeffs &m) {
+  MppiUpdateArgs a{};
+  a.plan = call.d_plan;
+  a.score = call.d_score;
+  a.out_plan = call.d_out_plan;
+  a.info = call.d_info;
+  a.n = call.n;
+  a.S = call.S;
+  a.b0 = (uint32_t)call.b0;
+  a.flags = call.flags;
+  a.seed = call.seed;
+  a.lambda = call.lambda;
+  a.collision_cost = call.collision_cost;
+  a.m = m;
+  a.limited = call.limits ? 1 : 0;
+  for (int r = 0; r < 4; ++r) {
+    a.lim_lo[r] = call.limits ? call.limits->lo[r] : 0.0;
+    a.lim_hi[r] = call.limits ? call.limits->hi[r] : 0.0;
+  }
+  return a;
+}
+
 __device__ __forceinline__ MppiMin mppi_min_from(const MppiMin &f, int off) {
   MppiMin o;
   o.key = __shfl_xor(f.key, off);
@@ -475,7 +504,7 @@ __device__ __forceinline__ MppiMin mppi_min_from(const MppiMin &f, int off) {
   return o;
 }
 
-// One block of THREADS = mppi_update_threads(S) lanes per plan: grid B.  Static LDS: the plan's weights (32 KB at the cap) and the
+// One block of THREADS = mppi_update_lanes(S) lanes (mppi_launch.h) per plan: grid B.  Static LDS: the plan's weights (32 KB at the cap) and the
 // wavefronts' partial sums of MPPI_CHUNK knots -- nothing that grows with n.  A lane carries the recursion state of its (at most four)
 // samples in registers through the knots, redrawing what the flight drew.
 template <int THREADS>

@@ -1,5 +1,6 @@
 // mppi_launch.h -- what mppi.hip gives the rest of the library: the launches of k_mppi_flight and k_mppi_update (mppi_kernels.h) for
-// qilqr_mppi_flight_device and qilqr_mppi_update_device, the rule of what those calls refuse, and the rule of their grids.  Declarations
+// qilqr_mppi_flight_device and qilqr_mppi_update_device, the rule of what those calls refuse, and the rule of their grids (the one
+// statement of the update's block size, which mppi_adapt.hip and the host programs of tests/ use too).  Declarations
 // and host code only -- no device code enters the translation unit that includes this (ilqr_capi.hip through host/caller_arrays.h);
 // hidden: not part of the C ABI.  The rules compile under g++ (tests/host_mppi_harness.cpp).
 #pragma once
@@ -7,6 +8,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "ranges.h"
 
@@ -18,14 +20,27 @@ inline long mppi_flight_blocks(long B, long S) {
   const long blocks = B * ((S + 63) / 64);
   return blocks > 0x7fffffffl ? 0 : blocks;
 }
-// k_mppi_update: one block per plan of the power of two >= S lanes, 64 at the least and 1024 at the most (mppi_kernels.h:
-// mppi_update_threads is the same rule where the kernels are compiled); a lane carries cdiv(S, lanes) samples, 4 at S = 4096
+// k_mppi_update and k_mppi_adapt: one block per plan of the power of two >= S lanes, 64 at the least and 1024 at the most -- THE rule,
+// for the launches and for the host programs of tests/; a lane carries cdiv(S, lanes) samples, 4 at S = 4096 (a lane without a sample
+// folds nothing and adds +0 to the sums)
 inline int mppi_update_lanes(long S) {
   int T = 64;
   while (T < S && T < 1024) T <<= 1;
   return T;
 }
+inline int mppi_update_threads(int S) { return mppi_update_lanes(S); }  // (the name mppi_kernels.h had for it: host programs written against that)
 inline int mppi_samples_per_lane(long S) { return (int)((S + mppi_update_lanes(S) - 1) / mppi_update_lanes(S)); }
+// go(std::integral_constant<int, mppi_update_lanes(S)>): the block size as the template argument of those kernels
+template <typename Go>
+auto with_update_lanes(long S, Go &&go) {
+  switch (mppi_update_lanes(S)) {
+    case 64: return go(std::integral_constant<int, 64>{});
+    case 128: return go(std::integral_constant<int, 128>{});
+    case 256: return go(std::integral_constant<int, 256>{});
+    case 512: return go(std::integral_constant<int, 512>{});
+    default: return go(std::integral_constant<int, 1024>{});
+  }
+}
 
 // ---- the refusals, from facts alone (no device): null when the call is admitted, else the reason.  ONE rule for both calls; `update`
 // says which.  THE ORDER:

@@ -2,7 +2,7 @@
 """Diagnostic: A/B of builds of the library on ONE box, in ONE process, interleaved (boxes of the pool differ by a few
 percent; runs minutes apart on one box by about one): whole device-resident batch solves (no events: the number `value`
 is made of) and, in a second pass, the average launch time of each kernel of the rounds (events on every launch).
-usage (repository root): PYTHONPATH=. python3 profiles/microbench/ab.py [B=1024] [N=100] [seed=2] name1=path1.so name2=path2.so ...
+usage (repository root): PYTHONPATH=. python3 profiles/microbench/ab.py [B=1024] [N=100] [seed=2] [reps=5] [raw=1] name1=path1.so name2=path2.so ...
        (a bare name means quadrotorilqr_amd/lib/libquadrotor_ilqr_<name>.so; "product" the product library)"""
 import importlib.util
 import os
@@ -26,7 +26,7 @@ def binding(path, tag):
 
 
 def main():
-    B, N, seed, reps, extra = 1024, 100, 2, 5, {}
+    B, N, seed, reps, extra, raw = 1024, 100, 2, 5, {}, 0
     libs = []
     for a in sys.argv[1:]:
         k, _, v = a.partition("=")
@@ -38,6 +38,8 @@ def main():
             seed = int(v)
         elif k == "reps":
             reps = int(v)
+        elif k == "raw":
+            raw = int(v)
         elif k in ("force_general", "single_wave_rollout", "streams", "persistent"):
             extra[k] = int(v)
         else:
@@ -83,6 +85,10 @@ def main():
         print(f"{name:12s} B={B} N={N}: {np.median(t):7.3f} ms per solve (min {t.min():.3f}, max {t.max():.3f}) = {B / np.median(t) * 1e3:9.0f} solves/s | "
               f"backward {p['backward_ms'] * 1e3 / max(p['backward_launches'], 1):6.2f} us  rollout {p['rollout_ms'] * 1e3 / max(p['rollout_launches'], 1):6.2f} us  "
               f"linearize {p['linearize_ms'] * 1e3 / max(p['linearize_launches'], 1):6.2f} us  ({p['backward_launches'] // 4} rounds) | max rel cost diff vs first {times['_dc'][name]:.1e}")
+    if raw:  # every alternation's value (the mean of its four solves), their mean and their standard deviation: the run-to-run spread
+        for name, _ in libs:
+            t = np.array(times[name]) * 1e3
+            print(f"{name:12s} B={B} raw ms: {' '.join(f'{x:.3f}' for x in t)} | mean {t.mean():.4f} sd {t.std(ddof=1):.4f}")
 
 
 if __name__ == "__main__":

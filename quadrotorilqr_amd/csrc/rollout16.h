@@ -8,7 +8,8 @@
 //   * every product with a matrix that does not depend on the state -- the nominal rotation R_n^T, the left
 //     multiplication by conj(q_n), the 4 x 12 feedback gain, I, dt I^-1, dt I^-1 arms -- is one
 //     v_fmac_f64_dpp row_newbcast per INPUT component (the lane holds its row of the matrix, the broadcast brings
-//     the component): 4 x 12 gains = 12 instructions instead of 52, a nominal quaternion product 4 instead of 28;
+//     the component): 4 x 12 gains = 12 instructions instead of 52, a nominal quaternion product 4 instead of 28; chains that do
+//     not depend on each other are issued in turn (WaveExt below), since a lone wavefront pays a chain's latency term by term;
 //   * the seven polynomials of the knot (cos, sinc, two Jacobian coefficients of Exp; the two halves of asin for
 //     Log) are evaluated side by side in different lanes with per-lane coefficient registers (one Estrin pass);
 //   * cross products are done four at a time: three-vectors sit in lanes 0..2 of a quad, a x b = a' b'' - a'' b'
@@ -119,6 +120,76 @@ QILQR_HD void make_rconsts(const ModelConsts<double> &c, RConsts<W> &k) {
   k.L1 = W::mconst([](int l) { return (l & 15) == 1; });
   k.L2 = W::mconst([](int l) { return (l & 15) == 2; });
   k.L3 = W::mconst([](int l) { return (l & 15) == 3; });
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// INDEPENDENT broadcast-multiply-add chains, two or three side by side.  A lone wavefront issues in order, so a chain alone pays the latency
+// of a dependent fp64 multiply-add per term; chains that take turns pay the issue rate.  A step has 35 such multiply-adds in 11 chains, and
+// 32 of them stand in four groups whose sources are ready together: qd | td (b_log), u2 | u3 | I omega (a_pre), u1 | u0 | gravity and
+// v_lin | omega (a_post); only omega - dt I^-1 (omega x I omega) is alone.  Every accumulator receives its own terms in the order of
+// W::dotN, so a group changes no bit.  The definitions here are made of the policy's own members, so every policy has them (the host
+// policies of the tests take these); DevWave specialises WaveExt with one asm block per group (rollout16_kernel.h).
+// Measured on configs[1], B = 1024 / a lone trajectory (profiles/r07_rollout_chains.txt; the phases' cycles: DESIGN.md section 4): a solve
+// 4.597 -> 4.550 / 2.029 -> 2.017 ms.  Two more changes of the step kept its bits and were taken out again, because neither was faster
+// than the parent's run-to-run spread: the rotation by two as ONE quad_perm from the original value (instead of a rotation of a rotation),
+// and the cross product as a rotation of fma(a, b', -(a' b)), which needs no a''.
+template <class W>
+struct WaveExt {
+  typedef typename W::V V;
+  // a += sum_c sa[lane LA + c] a_c (four terms), b += sum_c sb[lane LB + c] b_c (three)
+  template <int LA, int LB>
+  static QILQR_HD void dot43(V &a, const V &sa, const V &a0, const V &a1, const V &a2, const V &a3, V &b, const V &sb, const V &b0, const V &b1,
+                             const V &b2) {
+    a = W::template dot4<LA>(a, sa, a0, a1, a2, a3);
+    b = W::template dot3<LB>(b, sb, b0, b1, b2);
+  }
+  // four terms each
+  template <int LA, int LB>
+  static QILQR_HD void dot44(V &a, const V &sa, const V &a0, const V &a1, const V &a2, const V &a3, V &b, const V &sb, const V &b0, const V &b1,
+                             const V &b2, const V &b3) {
+    a = W::template dot4<LA>(a, sa, a0, a1, a2, a3);
+    b = W::template dot4<LB>(b, sb, b0, b1, b2, b3);
+  }
+  // three chains of three terms
+  template <int LA, int LB, int LC>
+  static QILQR_HD void dot333(V &a, const V &sa, const V &a0, const V &a1, const V &a2, V &b, const V &sb, const V &b0, const V &b1, const V &b2,
+                              V &c, const V &sc, const V &c0, const V &c1, const V &c2) {
+    a = W::template dot3<LA>(a, sa, a0, a1, a2);
+    b = W::template dot3<LB>(b, sb, b0, b1, b2);
+    c = W::template dot3<LC>(c, sc, c0, c1, c2);
+  }
+  // three, three and two terms
+  template <int LA, int LB, int LC>
+  static QILQR_HD void dot332(V &a, const V &sa, const V &a0, const V &a1, const V &a2, V &b, const V &sb, const V &b0, const V &b1, const V &b2,
+                              V &c, const V &sc, const V &c0, const V &c1) {
+    a = W::template dot3<LA>(a, sa, a0, a1, a2);
+    b = W::template dot3<LB>(b, sb, b0, b1, b2);
+    c = W::template dot2<LC>(c, sc, c0, c1);
+  }
+};
+template <class W, int LA, int LB>
+QILQR_HD void dot43_pair(typename W::V &a, const typename W::V &sa, const typename W::V &a0, const typename W::V &a1, const typename W::V &a2,
+                         const typename W::V &a3, typename W::V &b, const typename W::V &sb, const typename W::V &b0, const typename W::V &b1,
+                         const typename W::V &b2) {
+  WaveExt<W>::template dot43<LA, LB>(a, sa, a0, a1, a2, a3, b, sb, b0, b1, b2);
+}
+template <class W, int LA, int LB>
+QILQR_HD void dot4_pair(typename W::V &a, const typename W::V &sa, const typename W::V &a0, const typename W::V &a1, const typename W::V &a2,
+                        const typename W::V &a3, typename W::V &b, const typename W::V &sb, const typename W::V &b0, const typename W::V &b1,
+                        const typename W::V &b2, const typename W::V &b3) {
+  WaveExt<W>::template dot44<LA, LB>(a, sa, a0, a1, a2, a3, b, sb, b0, b1, b2, b3);
+}
+template <class W, int LA, int LB, int LC>
+QILQR_HD void dot3_triple(typename W::V &a, const typename W::V &sa, const typename W::V &a0, const typename W::V &a1, const typename W::V &a2,
+                          typename W::V &b, const typename W::V &sb, const typename W::V &b0, const typename W::V &b1, const typename W::V &b2,
+                          typename W::V &c, const typename W::V &sc, const typename W::V &c0, const typename W::V &c1, const typename W::V &c2) {
+  WaveExt<W>::template dot333<LA, LB, LC>(a, sa, a0, a1, a2, b, sb, b0, b1, b2, c, sc, c0, c1, c2);
+}
+template <class W, int LA, int LB, int LC>
+QILQR_HD void dot332_triple(typename W::V &a, const typename W::V &sa, const typename W::V &a0, const typename W::V &a1, const typename W::V &a2,
+                            typename W::V &b, const typename W::V &sb, const typename W::V &b0, const typename W::V &b1, const typename W::V &b2,
+                            typename W::V &c, const typename W::V &sc, const typename W::V &c0, const typename W::V &c1) {
+  WaveExt<W>::template dot332<LA, LB, LC>(a, sa, a0, a1, a2, b, sb, b0, b1, b2, c, sc, c0, c1);
 }
 
 // a x b for three-vectors in lanes j = 0..2 of every quad, given the rotations a' (j <- j + 1) and a'' (j <- j + 2) of a;
@@ -257,7 +328,11 @@ QILQR_HD void b_log(const RConsts<W> &k, typename W::V TT, typename W::V QQ, con
   typedef typename W::M M;
   const double eps = Eps<double>::manif;
   // ---- rotation part: qd = conj(q_n) q in Q0 (x, y, z, w)
-  V qd = W::template dot4<0>(V(0.0), QQ, op[OP_LQ + 0], op[OP_LQ + 1], op[OP_LQ + 2], op[OP_LQ + 3]);
+  // (with it, side by side: td = R_n^T (t - t_n) in Q0, which needs nothing of the Log)
+  const V dT = TT - op[OP_TN];
+  V qd = V(0.0);
+  TD = V(0.0);
+  dot43_pair<W, 0, 4>(qd, QQ, op[OP_LQ + 0], op[OP_LQ + 1], op[OP_LQ + 2], op[OP_LQ + 3], TD, dT, op[OP_RT + 0], op[OP_RT + 1], op[OP_RT + 2]);
   V sq = qd * qd;
   V s2 = W::template bc<0>(sq) + W::template bc<1>(sq);
   s2 = s2 + W::template bc<2>(sq);
@@ -303,9 +378,6 @@ QILQR_HD void b_log(const RConsts<W> &k, typename W::V TT, typename W::V QQ, con
     if (QILQR_RARE(W::any(closed))) cJ = W::jinv_closed(closed, th2, cJ);
     cJ = W::sel(small, V(0.0), cJ);
   }
-  // ---- td = R_n^T (t - t_n) in Q0
-  const V dT = TT - op[OP_TN];
-  TD = W::template dot3<4>(V(0.0), dT, op[OP_RT + 0], op[OP_RT + 1], op[OP_RT + 2]);
   TH4 = W::fma(k.M3, th, k.MW * cJ);
 }
 // control wave: rho = td - theta x td / 2 + c theta x (theta x td) in Q0, from the pose wave's (TH4, TD)
@@ -347,10 +419,13 @@ template <class W>
 QILQR_HD void a_pre(const RConsts<W> &k, typename W::V VL, typename W::V VW, const typename W::V *op, APre<W> &r) {
   typedef typename W::V V;
   const V dvl = VL - op[OP_VNL], dvw = VW - op[OP_VNW];
-  r.u2 = W::template dot3<0>(V(0.0), dvl, op[OP_K + 6], op[OP_K + 7], op[OP_K + 8]);
-  r.u3 = W::template dot3<8>(V(0.0), dvw, op[OP_K + 9], op[OP_K + 10], op[OP_K + 11]);  // (v_nom's angular part sits in Q2)
+  // three independent chains side by side: the two velocity terms of the control law (v_nom's angular part sits in Q2) and I omega in Q2
+  V IW = V(0.0);
+  r.u2 = V(0.0);
+  r.u3 = V(0.0);
+  dot3_triple<W, 0, 8, 0>(r.u2, dvl, op[OP_K + 6], op[OP_K + 7], op[OP_K + 8], r.u3, dvw, op[OP_K + 9], op[OP_K + 10], op[OP_K + 11], IW, VW, k.IC[0],
+                          k.IC[1], k.IC[2]);
   r.st0 = W::fma(k.MQ2_3, VW, k.MQ0_3 * VL);
-  const V IW = W::template dot3<0>(V(0.0), VW, k.IC[0], k.IC[1], k.IC[2]);  // I omega in Q2
   const V A1 = k.SA * VW;  // [0 | . | omega | 0]
   const V A1p = W::rot1(A1), A1pp = W::rot1(A1p);
   const V C1 = cross_rot<W>(A1p, A1pp, IW);  // Q2: omega x I omega
@@ -364,16 +439,18 @@ QILQR_HD typename W::V a_post(const RConsts<W> &k, const APre<W> &r, typename W:
                               typename W::V VL, const typename W::V *op, bool advance, typename W::V &VLn, typename W::V &VWn) {
   typedef typename W::V V;
   const V RH = RHO_DONE ? TD : a_rho<W>(TH, TD);  // (lane j = 3 of TH holds the Jacobian coefficient: the control law broadcasts lanes 0..2 only)
-  const V u1 = W::template dot3<0>(V(0.0), TH, op[OP_K + 3], op[OP_K + 4], op[OP_K + 5]);
-  const V u0 = W::template dot3<0>(op[OP_U0], RH, op[OP_K + 0], op[OP_K + 1], op[OP_K + 2]);
+  // the pose terms of the control law and, beside them, gravity in the body frame -- (z, w, x, .) and (w, z, y, .) of q -- which needs nothing
+  // of them (on the step after the last knot it is computed and not used)
+  V u1 = V(0.0), u0 = op[OP_U0], aL = VL + k.GRAVC;
+  dot332_triple<W, 0, 0, 0>(u1, TH, op[OP_K + 3], op[OP_K + 4], op[OP_K + 5], u0, RH, op[OP_K + 0], op[OP_K + 1], op[OP_K + 2], aL, QQ,
+                            k.S1 * W::template qperm<0xCE>(QQ), k.S2 * W::template qperm<0xDB>(QQ));
   const V UU = (u0 + u1) + (r.u2 + r.u3);  // valid in Q3 (the shared registers leave other operands' products elsewhere)
   const V st = W::fma(k.MQ3, UU, r.st0);
   if (!advance) return st;  // the reference's step after the last knot is computed and discarded (ilqr.hh:168)
-  // gravity in the body frame: (z, w, x, .) and (w, z, y, .) of q
-  const V aL = W::template dot2<0>(VL + k.GRAVC, QQ, k.S1 * W::template qperm<0xCE>(QQ), k.S2 * W::template qperm<0xDB>(QQ));
-  // J_u u: rows 8..11 of the constant control Jacobian (thrust along body z, torques)
-  VLn = W::template dot4<12>(aL, UU, k.GLz, k.GLz, k.GLz, k.GLz);
-  VWn = W::template dot4<12>(r.aW, UU, k.GW[0], k.GW[1], k.GW[2], k.GW[3]);
+  // J_u u: rows 8..11 of the constant control Jacobian (thrust along body z, torques), the two chains side by side
+  VLn = aL;
+  VWn = r.aW;
+  dot4_pair<W, 12, 12>(VLn, UU, k.GLz, k.GLz, k.GLz, k.GLz, VWn, UU, k.GW[0], k.GW[1], k.GW[2], k.GW[3]);
   return st;
 }
 

@@ -1,5 +1,6 @@
 // rollout16_kernel.h -- k_rollout16: sixteen lanes per trajectory, four trajectories per block (up to 4096 trajectories); its body is
-// rollout16_body.inc (k_backward_rollout and k_round contain it too); the lane-level arithmetic is rollout16.h.
+// rollout16_body.inc (k_backward_rollout and k_round contain it too); the lane-level arithmetic is rollout16.h.  DevWave is that
+// arithmetic's wave policy on the device; WaveExt<DevWave> below it issues the step's independent broadcast-multiply-add chains side by side.
 // Part of the device code of libquadrotor_ilqr.so (gfx950 only); ilqr_kernels.h includes every part.
 #pragma once
 
@@ -66,7 +67,6 @@ struct DevWave {
         : "+v"(acc) : "v"(src), "v"(m0), "v"(m1), "v"(m2), "v"(m3), "n"(L0), "n"(L0 + 1), "n"(L0 + 2), "n"(L0 + 3));
     return acc;
   }
-#undef QILQR_FMAC_DPP
   // permutation inside every quad of four lanes (two v_mov_b32_dpp quad_perm: fp64 DPP has row_newbcast only)
   template <int CTRL> static __device__ __forceinline__ V qperm(V x) {
     const long long v = __double_as_longlong(x);
@@ -97,6 +97,59 @@ struct DevWave {
   static __device__ __attribute__((noinline)) V log_closed(M c, V s2, V wq, V coeff) { return r16::log_closed_forms<DevWave>(c, s2, wq, coeff); }
   static __device__ __attribute__((noinline)) V jinv_closed(M c, V th2, V cJ) { return r16::jinv_closed_forms<DevWave>(c, th2, cJ); }
 };
+#undef QILQR_FMAC_DPP
+
+// The faster forms of r16::WaveExt (rollout16.h).  Independent chains in ONE asm block, their v_fmac_f64_dpp in turn: between two
+// multiply-adds of one accumulator stands one of another's, so a step pays the issue rate of an fp64 multiply-add instead of its latency
+// (a lone wavefront issues in order, and the compiler can move nothing into an asm block).  Every accumulator gets its terms in the order
+// of DevWave::dotN: the same bits.  Hazards: the DPP operand of every instruction is a chain's `src`, which no instruction of the block
+// writes; the accumulators are read as ordinary operands (interlocked).  So the rule of DevWave::dotN -- two wait states between the VALU
+// write of a register and a DPP read of it -- asks for the same s_nop 1 at the block's two ends and for nothing inside: a source may have
+// been written just ahead, and the accumulator written last may be the source of a DPP read right behind.
+#define R16_FMAC(acc, src, m, l) "v_fmac_f64_dpp " acc ", " src ", " m " row_newbcast:" l " row_mask:0xf bank_mask:0xf\n\t"
+namespace r16 {
+template <>
+struct WaveExt<DevWave> {
+  typedef double V;
+  template <int LA, int LB>
+  static __device__ __forceinline__ void dot43(V &a, V sa, V a0, V a1, V a2, V a3, V &b, V sb, V b0, V b1, V b2) {
+    asm("s_nop 1\n\t" R16_FMAC("%0", "%2", "%4", "%11") R16_FMAC("%1", "%3", "%8", "%15") R16_FMAC("%0", "%2", "%5", "%12")
+        R16_FMAC("%1", "%3", "%9", "%16") R16_FMAC("%0", "%2", "%6", "%13") R16_FMAC("%1", "%3", "%10", "%17")
+        R16_FMAC("%0", "%2", "%7", "%14") "s_nop 1"
+        : "+v"(a), "+v"(b)
+        : "v"(sa), "v"(sb), "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "n"(LA), "n"(LA + 1), "n"(LA + 2), "n"(LA + 3),
+          "n"(LB), "n"(LB + 1), "n"(LB + 2));
+  }
+  template <int LA, int LB>
+  static __device__ __forceinline__ void dot44(V &a, V sa, V a0, V a1, V a2, V a3, V &b, V sb, V b0, V b1, V b2, V b3) {
+    asm("s_nop 1\n\t" R16_FMAC("%0", "%2", "%4", "%12") R16_FMAC("%1", "%3", "%8", "%16") R16_FMAC("%0", "%2", "%5", "%13")
+        R16_FMAC("%1", "%3", "%9", "%17") R16_FMAC("%0", "%2", "%6", "%14") R16_FMAC("%1", "%3", "%10", "%18")
+        R16_FMAC("%0", "%2", "%7", "%15") R16_FMAC("%1", "%3", "%11", "%19") "s_nop 1"
+        : "+v"(a), "+v"(b)
+        : "v"(sa), "v"(sb), "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "v"(b3), "n"(LA), "n"(LA + 1), "n"(LA + 2),
+          "n"(LA + 3), "n"(LB), "n"(LB + 1), "n"(LB + 2), "n"(LB + 3));
+  }
+  template <int LA, int LB, int LC>
+  static __device__ __forceinline__ void dot333(V &a, V sa, V a0, V a1, V a2, V &b, V sb, V b0, V b1, V b2, V &c, V sc, V c0, V c1, V c2) {
+    asm("s_nop 1\n\t" R16_FMAC("%0", "%3", "%6", "%15") R16_FMAC("%1", "%4", "%9", "%18") R16_FMAC("%2", "%5", "%12", "%21")
+        R16_FMAC("%0", "%3", "%7", "%16") R16_FMAC("%1", "%4", "%10", "%19") R16_FMAC("%2", "%5", "%13", "%22")
+        R16_FMAC("%0", "%3", "%8", "%17") R16_FMAC("%1", "%4", "%11", "%20") R16_FMAC("%2", "%5", "%14", "%23") "s_nop 1"
+        : "+v"(a), "+v"(b), "+v"(c)
+        : "v"(sa), "v"(sb), "v"(sc), "v"(a0), "v"(a1), "v"(a2), "v"(b0), "v"(b1), "v"(b2), "v"(c0), "v"(c1), "v"(c2), "n"(LA), "n"(LA + 1),
+          "n"(LA + 2), "n"(LB), "n"(LB + 1), "n"(LB + 2), "n"(LC), "n"(LC + 1), "n"(LC + 2));
+  }
+  template <int LA, int LB, int LC>
+  static __device__ __forceinline__ void dot332(V &a, V sa, V a0, V a1, V a2, V &b, V sb, V b0, V b1, V b2, V &c, V sc, V c0, V c1) {
+    asm("s_nop 1\n\t" R16_FMAC("%0", "%3", "%6", "%14") R16_FMAC("%1", "%4", "%9", "%17") R16_FMAC("%2", "%5", "%12", "%20")
+        R16_FMAC("%0", "%3", "%7", "%15") R16_FMAC("%1", "%4", "%10", "%18") R16_FMAC("%2", "%5", "%13", "%21")
+        R16_FMAC("%0", "%3", "%8", "%16") R16_FMAC("%1", "%4", "%11", "%19") "s_nop 1"
+        : "+v"(a), "+v"(b), "+v"(c)
+        : "v"(sa), "v"(sb), "v"(sc), "v"(a0), "v"(a1), "v"(a2), "v"(b0), "v"(b1), "v"(b2), "v"(c0), "v"(c1), "n"(LA), "n"(LA + 1), "n"(LA + 2),
+          "n"(LB), "n"(LB + 1), "n"(LB + 2), "n"(LC), "n"(LC + 1));
+  }
+};
+}  // namespace r16
+#undef R16_FMAC
 
 // s_waitcnt vmcnt(0) as an instruction the compiler's wait-count pass sees (gfx9 encoding: vmcnt in bits 3:0 and 15:14,
 // expcnt 6:4 = 7 and lgkmcnt 11:8 = 15 left open).  Placed after the loads of a role's initial state: otherwise the pass may

@@ -179,6 +179,10 @@ struct R16Lds {
 __device__ __forceinline__ int r16_flag_read(R16Lds &sh, int which) {
   return __hip_atomic_load(&sh.flags[which], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+// Every lane has read the same word, and readfirstlane says so to the compiler: a test of the word is then a scalar compare and a scalar
+// branch.  (As a value per lane it makes every wait a divergent branch.  The steady state of r16_wave_X uses this; the other roles keep
+// the value per lane -- with it their kernels' registers stay as they were.)
+__device__ __forceinline__ int r16_uniform(int word) { return __builtin_amdgcn_readfirstlane(word); }
 __device__ __forceinline__ void r16_flag_post(R16Lds &sh, int which, int value, int lane) {
   asm volatile("" ::: "memory");
   if (lane == 0) __hip_atomic_store(&sh.flags[which], value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -257,24 +261,26 @@ __device__ __forceinline__ bool r16_handoff_finish(R16Lds &sh, int which, int ta
 // two youngest are complete (s_waitcnt vmcnt(2): a step's two stores are
 // the only ones the loop issues; memory operations of one kind complete in order; anything else the compiler might add there -- a spill --
 // would be younger still and only make the wait longer, never the announcement early), which stalls for nothing in the steady state.
+// r16_publish_chunk: the announcement of a knot that is not the wavefront's last (the steady state's steps need no other).
 template <int PUBLISH>
-__device__ __forceinline__ void r16_publish_stores(R16Lds &sh, int which, int i, int last, int lane) {
+__device__ __forceinline__ void r16_publish_chunk(R16Lds &sh, int which, int i, int lane) {
   if (PUBLISH == 2) {
-    if (i == last) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      r16_flag_post(sh, which, i + 1, lane);
-    } else if (i >= R16_CHUNK && (i & (R16_CHUNK - 2)) == 0) {  // (i = 16 k or 16 k + 1: the wavefront's knot i - 2 completes a chunk of sixteen)
+    if (__builtin_expect(i >= R16_CHUNK && (i & (R16_CHUNK - 2)) == 0, 0)) {  // (i = 16 k or 16 k + 1: the wavefront's knot i - 2 completes a chunk of sixteen)
       asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       r16_flag_post(sh, which, i - 1, lane);
     }
-    return;
+  } else if (__builtin_expect(((i >> 1) & 3) == 3 && i >= 16, 0)) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    r16_flag_post(sh, which, i + 1, lane);
   }
+}
+template <int PUBLISH>
+__device__ __forceinline__ void r16_publish_stores(R16Lds &sh, int which, int i, int last, int lane) {
   if (i == last) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     r16_flag_post(sh, which, i + 1, lane);
-  } else if (((i >> 1) & 3) == 3 && i >= 16) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    r16_flag_post(sh, which, i + 1, lane);
+  } else {
+    r16_publish_chunk<PUBLISH>(sh, which, i, lane);
   }
 }
 
@@ -435,9 +441,94 @@ __device__ __forceinline__ void r16_wave_X(R16Lds &sh, const ModelConsts<double>
     }
     return true;
   };
+  // A step of the STEADY STATE: knot i with i + 2 < n, its operands in `op`.  What `step` decides every time is fixed here: the step has a
+  // successor (advance), the knot is not the wavefront's last, the pose of knot i + 2 is wanted, the operands are in registers and those of
+  // the wavefront's next knot are read into `opn` on the straight line.
+  // It has NO way out: a return from inside the loop is one more exit of the loop, and the compiler gives a loop with several exits one exit
+  // and a flag per way out, set and tested along the straight line (they were a fifth of a step's instructions).  A wait that runs out -- the
+  // abort word is posted there, as ever -- only sets `lost`: the step goes on with the values it has, to the end of the pair of steps at the
+  // most (every later wait of it sees the abort word and ends at once), and the wavefront leaves behind them.  What it stores and hands on
+  // meanwhile belongs to a rollout that the abort word has already declared void.
+  bool lost = false;
+  int announce = R16_CHUNK + p;  // (PUBLISH = 2) the wavefront's next knot that announces a chunk
+  auto main_step = [&](int i, double (&op)[NOPS], double (&opn)[NOPS]) {
+    S *ok_ = out + (long)i * (9 * TILE2);
+    if (wp) ok_[opz] = (S)__builtin_fma(kc.MQ0, QQ, TT);  // [q | t] in one store
+    QSTAMP(0);
+    double TH4, TD;
+    b_log<DevWave>(kc, TT, QQ, op, TH4, TD);
+    int fv;
+    double v[2];
+    r16_handoff_request<2>(sh, R16_F_V, X_V, i & 3, fv, v, lane);  // (v_0: put there by this wavefront itself, in front of the loop)
+    const double RH = a_rho<DevWave>(TH4, TD);
+    QSTAMP(1);
+    if (__builtin_expect(r16_uniform(fv) < i, 0)) lost |= !r16_uniform(r16_read_handoff<2>(sh, R16_F_V, i, X_V, i & 3, v, lane));
+    QSTAMP(2);
+    APre<DevWave> pre;
+    a_pre<DevWave>(kc, v[0], v[1], op, pre);
+    double VLn = 0.0, VWn = 0.0;
+    const double st = a_post<DevWave, true>(kc, pre, TH4, RH, QQ, v[0], op, true, VLn, VWn);
+    sh.xch[X_V][(i + 1) & 3][0][lane] = VLn;
+    sh.xch[X_V][(i + 1) & 3][1][lane] = VWn;
+#ifdef QILQR_DIAG
+    if (i != g_r16_stall_knot)  // fault injection (qilqr_debug_set_rollout_stall): this hand-off is never announced
+#endif
+    r16_flag_post(sh, R16_F_V, i + 1, lane);
+    if (wa) ok_[oa] = (S)st;
+    if (PUBLISH == 2) {  // (r16_publish_chunk's knots, 16 k + p, counted instead of recognised)
+      if (__builtin_expect(i == announce, 0)) {
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        r16_flag_post(sh, R16_F_K0 + p, i - 1, lane);
+        announce += R16_CHUNK;
+      }
+    } else if (PUBLISH) {
+      r16_publish_chunk<PUBLISH>(sh, R16_F_K0 + p, i, lane);
+    }
+    QSTAMP(3);
+    int ft;
+    double t[2];
+    r16_handoff_request<2>(sh, R16_F_T, X_T, (i + 1) & 3, ft, t, lane);
+    double DQ, PP;
+    a_exp<DevWave>(kc, VLn, VWn, DQ, PP);
+    QSTAMP(4);
+    if (__builtin_expect(r16_uniform(ft) < i + 1, 0)) lost |= !r16_uniform(r16_read_handoff<2>(sh, R16_F_T, i + 1, X_T, (i + 1) & 3, t, lane));
+    QSTAMP(5);
+    // the operands of this wave's next knot: P is normally three knots ahead, and `seen` (read a step ago) says so; where it is not, wait
+    // here, out of line (P needs nothing of this step to produce knot i + 2: its slot has been free since v_{i-1} was posted)
+    if (__builtin_expect(seen < i + 3, 0)) lost |= !r16_uniform(r16_flag_wait(sh, R16_F_PROD, i + 3, seen, lane));
+#pragma unroll
+    for (int r = 0; r < NOPS; ++r) opn[r] = sh.ops[(i + 2) % R16_RING][r][lane];
+    seen = r16_uniform(r16_flag_read(sh, R16_F_PROD));
+    double TTn, QQn;
+    b_compose<DevWave>(kc, t[0], t[1], DQ, PP, TTn, QQn);
+    TT = TTn;
+    QQ = QQn;
+    sh.xch[X_T][(i + 2) & 3][0][lane] = TT;
+    sh.xch[X_T][(i + 2) & 3][1][lane] = QQ;
+    r16_flag_post(sh, R16_F_T, i + 2, lane);
+    QSTAMP(6);
+  };
   double opA[NOPS], opB[NOPS];
   bool haveA = false, haveB = false;
-  for (int i = p; i < n; i += 4) {
+  int i = p;
+  if (i + 4 < n) {  // the steady state, two steps at a time (the two operand register sets in turn: no copies, and no flag says which)
+    if (__builtin_expect(!r16_flag_wait(sh, R16_F_PROD, i + 1, seen, lane), 0)) return;
+    if (p == 0) {  // v_0 goes through its hand-off slot like every other v_i (the "v ready" word starts at 0: no knot is asked of it)
+      sh.xch[X_V][0][0][lane] = VL;
+      sh.xch[X_V][0][1][lane] = VW;
+    }
+#pragma unroll
+    for (int r = 0; r < NOPS; ++r) opA[r] = sh.ops[i % R16_RING][r][lane];
+    do {
+      main_step(i, opA, opB);
+      main_step(i + 2, opB, opA);
+      i += 4;
+    } while (!lost && i + 4 < n);
+    if (lost) return;
+    haveA = true;
+  }
+  // the wavefront's last one or two knots, and every n too short for the steady state: the general step
+  for (; i < n; i += 4) {
     if (!step(i, opA, haveA, opB, haveB)) return;
     if (i + 2 >= n) break;
     if (!step(i + 2, opB, haveB, opA, haveA)) return;

@@ -880,6 +880,14 @@ int qilqr_gather_schedule(int32_t B, int32_t n, const int32_t *devices, int32_t 
  * off for that call.  Waits for the handle's stream. */
 int qilqr_compaction_moves(qilqr_solver *s, int64_t *moves);
 
+/* k_round launches of this handle per instantiation k_round<LK, ROUNDS, SIX>, since the handle was created or since
+ * qilqr_profile_reset: counted on the host where a launch is enqueued, whatever qilqr_device_config.profile is (nothing is waited for).
+ * counts[5 * (LK - 1) + j]: LK the record kind of the cost half -- 1 dense symmetric Q with a non-zero pose x velocity block, 2
+ * symmetric Q with that block exactly zero, 3 diagonal Q -- and j = 0..4 for (ROUNDS, SIX) = (1, no), (1, yes), (2, no), (4, no),
+ * (4, yes): rounds in the launch, and whether its backward pass takes the six-wavefront form. */
+#define QILQR_ROUND_KERNELS 15
+int qilqr_round_launches(qilqr_solver *s, int32_t counts[15]);
+
 /* In words, which arithmetic and which kernels a batch solve of B problems on this handle uses: the reference's own forms or the
  * symmetric-weight forms (the choice is made by whether Q and R are bit-exactly symmetric and by force_general: see
  * qilqr_device_config.force_general), the integrator, the precision, the backward and rollout kernels, how a round is launched,
@@ -898,7 +906,8 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * qilqr_select_rule, QILQR_MC_RISK, QILQR_RISK_MAX_LEVELS, QILQR_RISK_MAX_SAMPLES, QILQR_RISK_COST, QILQR_RISK_CLEARANCE,
  * QILQR_SELECT_INFO, qilqr_mppi_flight_device, qilqr_mppi_update_device, qilqr_mppi_rule, QILQR_MPPI_INFO,
  * QILQR_MPPI_FIRST_IS_NOMINAL, qilqr_mppi_flight_spread_device, qilqr_mppi_adapt_device, qilqr_mppi_adapt_rule, qilqr_covariance_device,
- * qilqr_cov_rule, QILQR_COV, QILQR_COV_SUMMARY and QILQR_COV_WRENCH_HELD were added within version 7: no structure changed. */
+ * qilqr_cov_rule, QILQR_COV, QILQR_COV_SUMMARY, QILQR_COV_WRENCH_HELD, qilqr_round_launches and QILQR_ROUND_KERNELS were added within
+ * version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

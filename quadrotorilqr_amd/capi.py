@@ -50,6 +50,7 @@ MPPI_FIRST_IS_NOMINAL = 1  # QILQR_MPPI_FIRST_IS_NOMINAL: qilqr_mppi_rule.flags,
 COV = 144  # QILQR_COV: a knot's covariance, 12 x 12 row-major over the tangent [rho, theta, dv, dw] (covariance_device)
 COV_SUMMARY = 8  # QILQR_COV_SUMMARY: max sqrt(tr P), its knot, sqrt(tr P) at the last knot, max rotation deviation, smallest clearance z, its knot, its sphere, max control deviation
 COV_WRENCH_HELD = 1  # QILQR_COV_WRENCH_HELD: qilqr_cov_rule.flags, one wrench per flight
+ROUND_KERNELS = 15  # QILQR_ROUND_KERNELS: the k_round instantiations (round_launches)
 CL_STATS = 4  # QILQR_CL_STATS: max position error, max rotation error, |dx| at the last knot, clamped (knot, rotor) pairs (closed_loop)
 
 # every symbol include/quadrotor_ilqr.h declares
@@ -71,7 +72,7 @@ EXPORTS = (
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
     "qilqr_sharded_set_transport", "qilqr_sharded_transport", "qilqr_solve_batch_sharded_device", "qilqr_gather_schedule",
-    "qilqr_abi_version", "qilqr_compaction_moves", "qilqr_describe",
+    "qilqr_abi_version", "qilqr_compaction_moves", "qilqr_describe", "qilqr_round_launches",
 )
 
 
@@ -981,6 +982,13 @@ class QuadrotorILQRBatch:
         p = Profile()
         _check(load().qilqr_profile_get(self._h, C.byref(p)))
         return {f: getattr(p, f) for f, _ in Profile._fields_}
+
+    def round_launches(self):
+        """qilqr_round_launches: int32[15], the k_round launches per instantiation since the handle was created or since profile_reset();
+        index 5 * (LK - 1) + j, j = 0..4 for (ROUNDS, SIX) = (1, F), (1, T), (2, F), (4, F), (4, T)"""
+        counts = np.zeros(ROUND_KERNELS, dtype=np.int32)
+        _check(load().qilqr_round_launches(self._h, _ip(counts)))
+        return counts
 
 
 class QuadrotorILQRSharded:

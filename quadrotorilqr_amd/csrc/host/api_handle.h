@@ -222,6 +222,14 @@ int qilqr_profile_reset(qilqr_solver *s) {
     s->prof_n[k] = 0;
     s->prof_seen[k] = 0;
   }
+  for (int k = 0; k < QILQR_ROUND_KERNELS; ++k) s->round_launches[k] = 0;
+  return QILQR_OK;
+}
+
+int qilqr_round_launches(qilqr_solver *s, int32_t counts[QILQR_ROUND_KERNELS]) {
+  if (!s || !counts) return fail(QILQR_ERR_INVALID_ARG, "null argument");
+  // (counted on the host where the launch is enqueued: nothing to wait for)
+  for (int k = 0; k < QILQR_ROUND_KERNELS; ++k) counts[k] = s->round_launches[k];
   return QILQR_OK;
 }
 

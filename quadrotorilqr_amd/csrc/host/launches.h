@@ -224,17 +224,18 @@ int launch_rollout(qilqr_solver *s, long B, long n, int need_flag, long ordinal 
 // into the counter set of its parity; the launch publishes the round before it.
 int launch_round(qilqr_solver *s, long B, long n, long round, bool publish_prev, int rounds, bool six = false) {
   const ModelConsts<double> *cp = (const ModelConsts<double> *)s->d_consts;
-  if (rounds == 2) six = false;  // (the six-wavefront form is instantiated for launches of one and of four rounds)
+  six = round_instance(RoundForm{rounds, six}).six;  // (the six-wavefront form is instantiated for launches of one and of four rounds)
   const dim3 grid(cdiv(B, 4)), block(six ? 384 : 320);
   BatchState st = s->st;
   int *base = s->st.counters;
   st.counters = base + (round & 1) * COUNT_WORDS;
   int *prev = base + ((round + 1) & 1) * COUNT_WORDS;
   const int prev_round = publish_prev ? (int)((round - 1) & 0x3fffffff) : -1;
-  const int lk = std::max(s->route.lin_kind, 1);  // (the record kind of k_linearize: k_round takes the symmetric ones)
+  const int lk = round_lk(s->route);
 #define QILQR_LAUNCH_ROUND(LK, R, SIX)                                                                                                          \
   case LK * 16 + R * 2 + SIX:                                                                                                                     \
     launch(s, K_BACKWARD, (k_round<LK, R, SIX>), grid, block, s->consts, cp, s->params, st, (int)B, (int)n, prev, prev_round);                    \
+    ++s->round_launches[round_slot(LK, R, SIX)]; /* (qilqr_round_launches: the slot of the case's own template arguments) */                    \
     break
   switch (lk * 16 + rounds * 2 + (six ? 1 : 0)) {
     QILQR_LAUNCH_ROUND(3, 4, true); QILQR_LAUNCH_ROUND(2, 4, true); QILQR_LAUNCH_ROUND(1, 4, true);

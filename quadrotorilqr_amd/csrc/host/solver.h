@@ -128,6 +128,8 @@ struct qilqr_solver {
   double prof_ms[K_KINDS] = {0, 0, 0, 0, 0};
   unsigned prof_seen[K_KINDS] = {0, 0, 0, 0, 0};  // launches of each kind seen by the sampler
   int prof_n[K_KINDS] = {0, 0, 0, 0, 0};
+  // k_round launches per instantiation since the last reset (launch_round counts, whatever dev.profile is; qilqr_round_launches)
+  int32_t round_launches[QILQR_ROUND_KERNELS] = {};
   int num_cus = 256;  // compute units of the device (grid of the persistent solve)
   // compaction of the live trajectories (k_compact_plan / k_compact_move): on for the duration of a device-resident batch
   // solve that qualifies (compaction_for_call), with the caller's result arrays for the trajectories that leave early

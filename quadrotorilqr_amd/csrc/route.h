@@ -268,6 +268,15 @@ inline RoundForm round_form(const Route &r, bool several, bool forced, unsigned 
   f.six = forced ? (r.force_general == 8 || (r.force_general == 0 && sparse)) : sparse;
   return f;
 }
+// LK of the instantiation a launch takes (launch_round): the record kind of k_linearize; k_round takes the symmetric ones
+inline int round_lk(const Route &r) { return std::max(r.lin_kind, 1); }
+// ... and its form: the six-wavefront form is instantiated for launches of one and of four rounds
+inline RoundForm round_instance(RoundForm f) {
+  if (f.rounds == 2) f.six = false;
+  return f;
+}
+// its slot in qilqr_round_launches' counts: 5 (LK - 1) + j, j = 0..4 for (rounds, six) = (1, no), (1, yes), (2, no), (4, no), (4, yes)
+constexpr int round_slot(int lk, int rounds, bool six) { return 5 * (lk - 1) + (rounds == 1 ? (six ? 1 : 0) : rounds == 2 ? 2 : (six ? 4 : 3)); }
 
 // When a compacted (sub-)batch changes over to the combined launch for the rest of its solve.
 struct TailFuse {

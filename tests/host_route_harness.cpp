@@ -1,6 +1,7 @@
 // Host build of quadrotorilqr_amd/csrc/route.h for tests/test_route_cpu.py: one row of tests/golden/routes.json's inputs in, the
 // route's choices out, in the table's encoding; and the keys of the k_linearize instantiations the rule admits (hr_lin_keys), for
-// tests/golden/linearize_keys.json.  Test scaffolding only.
+// tests/golden/linearize_keys.json; and the k_round instantiation of a launch (hr_round_form), for tests/test_round_cases_cpu.py.  Test
+// scaffolding only.
 #include "../quadrotorilqr_amd/csrc/route.h"
 
 using namespace qilqr;
@@ -109,6 +110,38 @@ extern "C" int hr_lin_route(const long *in, long *out) {
   *o++ = ext;
   *o++ = r.backward;
   *o++ = lin_instantiated(lin_key(r.lin_kind, r.integrator, r.tiled, r.f32, ext));
+  return (int)(o - out);
+}
+
+// The k_round instantiation of one launch of a solve's single-stream rounds (host/batch_solve.h, run_solve), from the RouteInputs a handle
+// makes of itself (tests/round_cases.py, predicates) and what the host knows when it enqueues the launch: plan_route, then
+// round_form with forced = true, then the rules by which launch_round picks among the instantiations (round_lk, round_instance) and the slot
+// it counts the launch in (round_slot).
+// in:  {symmetric, q_diag, layout_kind, force_general, round_launch, rounds_per_launch, B, desired_batch, cost_hist, early_out,
+//       several (the launches may hold several rounds), seen_active (the last count of running trajectories the host has read), used (slots)}
+// out: {the rounds are k_round launches (the combined launch, no compaction), LK, ROUNDS, SIX, slot in qilqr_round_launches' counts}
+extern "C" int hr_round_form(const long *in, long *out) {
+  RouteInputs ri;
+  ri.symmetric = in[0];
+  ri.q_diag = in[1];
+  ri.layout_kind = (int)in[2];
+  ri.dev.force_general = (int)in[3];
+  ri.dev.round_launch = (int)in[4];
+  ri.dev.rounds_per_launch = (int)in[5];
+  ri.dev.sync_every = 2;
+  CallFacts call;
+  call.desired_batch = in[7];
+  call.cost_hist = in[8];
+  call.early_out = in[9];
+  const Route r = plan_route(ri, in[6], call);
+  const RoundForm f = round_instance(round_form(r, in[10] != 0, /*forced=*/true, (unsigned)in[11], in[12]));
+  const int lk = round_lk(r);
+  long *o = out;
+  *o++ = r.combined && !r.compact && r.round_kernel;
+  *o++ = lk;
+  *o++ = f.rounds;
+  *o++ = f.six;
+  *o++ = round_slot(lk, f.rounds, f.six);
   return (int)(o - out);
 }
 

@@ -1,7 +1,8 @@
 // closed_loop.hip -- the translation unit of k_closed_loop (closed_loop_kernels.h), the device side of qilqr_closed_loop[_device].  Its own
 // unit for shift.hip's reason: the call works on the caller's arrays only -- no workspace, no BatchState, no route -- and ilqr_capi.hip's
 // device code stays what it was.  Exports launch_closed_loop, which host/caller_arrays.h
-// reaches through launch_closed_loop_scored, and closed_loop_form, the form and grid of both closed-loop units (closed_loop_launch.h; hidden).
+// reaches through launch_closed_loop_scored, and closed_loop_form and closed_loop_args, the form and grid and the first argument record of
+// both closed-loop units (closed_loop_launch.h; hidden).
 #include <hip/hip_runtime.h>
 
 #include "closed_loop_kernels.h"
@@ -35,8 +36,12 @@ bool closed_loop_form(int B, int S, bool *shared, dim3 *grid) {
   return true;
 }
 
+ClosedLoopArgs closed_loop_args(const ClosedLoopLaunch &call) {
+  return ClosedLoopArgs{call.d_plan, call.d_gains, call.d_x0, call.d_out_traj, call.d_out_stats, call.B, call.n, call.S, call.i0, call.i1};
+}
+
 hipError_t launch_closed_loop(hipStream_t stream, const ModelConsts<double> &consts, const ClosedLoopLaunch &call) {
-  const ClosedLoopArgs a{call.d_plan, call.d_gains, call.d_x0, call.d_out_traj, call.d_out_stats, call.B, call.n, call.S, call.i0, call.i1};
+  const ClosedLoopArgs a = closed_loop_args(call);
   bool shared;
   dim3 grid;
   if (!closed_loop_form(call.B, call.S, &shared, &grid)) return hipErrorInvalidValue;

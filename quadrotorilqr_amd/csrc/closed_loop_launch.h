@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "call_parts.h"
 #include "ranges.h"
 
 namespace qilqr {
@@ -72,11 +73,11 @@ inline const char *closed_loop_scored_refusal(const ClosedLoopScoredCall &s, boo
     return "closed loop: the per-problem models must have been set for B * S samples (model b S + j flies sample (b, j))";
   if (c.out_score) {
     if (s.pobs_B > 0 && s.pobs_B != c.B) return "closed loop: the per-problem obstacles were set for another B than this call's (the score reads row b of that table)";
-    if (!s.desired && c.i1 >= s.n_desired - s.k0) {
+    if (!s.desired && beyond_desired(c.i1, s.n_desired, s.k0)) {
       *length = true;
       return "closed loop: the scored knots reach beyond the handle's desired trajectory";
     }
-    if (s.n_sched > 0 && c.i1 >= s.n_sched - s.k0) {
+    if (beyond_schedule(c.i1, s.n_sched, s.k0)) {
       *length = true;
       return "closed loop: the scored knots reach beyond the state-weight schedule";
     }
@@ -118,22 +119,18 @@ __attribute__((visibility("hidden"))) bool closed_loop_form(int B, int S, bool *
 // enqueues the launch on `stream` and returns what the launch returned; nothing is waited for
 __attribute__((visibility("hidden"))) hipError_t launch_closed_loop(hipStream_t stream, const ModelConsts<double> &consts, const ClosedLoopLaunch &call);
 
+// the kernels' first argument record of a call (closed_loop_kernels.h), for both units
+struct ClosedLoopArgs;
+__attribute__((visibility("hidden"))) ClosedLoopArgs closed_loop_args(const ClosedLoopLaunch &call);
+
 // the scored call: the plain call's launch record and what the score and the wrench read (every pointer a device one).  A call with
 // neither a wrench nor a score goes to launch_closed_loop.
 struct ClosedLoopScoredLaunch {
   ClosedLoopLaunch base;
   const double *d_wrench;   // [B][S][n_w][6], or null
   int n_w;
-  double *d_out_score;      // [B][S][4], or null: no score (then nothing below is read)
-  const double *d_desired;  // the first desired knot of the window: per plan [B][n][18] (desired_step = n * 18), or the handle's (0)
-  long desired_step;
-  const double *d_q;        // the state weights of the window's first knot, 16-byte aligned: a schedule's (q_step = 144) or the handle's Q (0)
-  int q_step;
-  const double *d_shared;   // the handle's sphere tables
-  int n_shared;
-  const double *d_own;
-  const int *d_own_counts;
-  int own_K;
+  double *d_out_score;      // [B][S][4], or null: no score (then `score` is not read)
+  ScoreOperands score;      // from the window's first knot (call_parts.h)
 };
 __attribute__((visibility("hidden"))) hipError_t launch_closed_loop_scored(hipStream_t stream, const ModelConsts<double> &consts, const ClosedLoopScoredLaunch &call);
 

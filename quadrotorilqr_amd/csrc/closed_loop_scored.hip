@@ -1,7 +1,7 @@
 // closed_loop_scored.hip -- the translation unit of k_closed_loop_scored (closed_loop_scored_kernels.h), the device side of
 // qilqr_closed_loop_scored[_device].  A unit beside closed_loop.hip, whose sixteen kernels stay what they were: the 48 instantiations here
 // are {wrench, score, both} x k_closed_loop's sixteen.  Exports one hidden function, launch_closed_loop_scored (closed_loop_launch.h), which
-// host/caller_arrays.h calls; the form and the grid are closed_loop.hip's closed_loop_form.
+// host/caller_arrays.h calls; the form, the grid and the first argument record are closed_loop.hip's (closed_loop_form, closed_loop_args).
 #include <hip/hip_runtime.h>
 
 #include "closed_loop_scored_kernels.h"
@@ -31,8 +31,8 @@ hipError_t scored_switch(hipStream_t stream, const ModelConsts<double> &c, const
 hipError_t launch_closed_loop_scored(hipStream_t stream, const ModelConsts<double> &consts, const ClosedLoopScoredLaunch &s) {
   const ClosedLoopLaunch &call = s.base;
   if (!s.d_wrench && !s.d_out_score) return launch_closed_loop(stream, consts, call);  // the existing instantiations: the parent's bits
-  const ClosedLoopArgs a{call.d_plan, call.d_gains, call.d_x0, call.d_out_traj, call.d_out_stats, call.B, call.n, call.S, call.i0, call.i1};
-  const ClosedLoopScoreArgs e{s.d_wrench, s.n_w, s.d_desired, s.desired_step, s.d_q, s.q_step, s.d_shared, s.n_shared, s.d_own, s.d_own_counts, s.own_K, s.d_out_score};
+  const ClosedLoopArgs a = closed_loop_args(call);
+  const ClosedLoopScoreArgs e{s.d_wrench, s.n_w, s.score, s.d_out_score};
   bool shared;
   dim3 grid;
   if (!closed_loop_form(call.B, call.S, &shared, &grid)) return hipErrorInvalidValue;

@@ -18,6 +18,7 @@
 // Part of closed_loop_scored.hip's translation unit (gfx950 only).
 #pragma once
 
+#include "call_parts.h"
 #include "closed_loop_kernels.h"
 
 #if defined(__clang__)
@@ -30,15 +31,7 @@ namespace qilqr {
 struct ClosedLoopScoreArgs {
   const double *wrench;    // [B][S][n_w][6], or null (then WRENCH is off)
   int n_w;                 // 1 or n
-  const double *desired;   // knot i of problem b is desired + b * desired_step + i * 18
-  long desired_step;       // n * 18 (one per plan), or 0 (the handle's, from its horizon start)
-  const double *q;         // knot i's state weights are q + i * q_step
-  int q_step;              // 144 (a schedule, from the horizon start), or 0 (the handle's Q)
-  const double *shared;    // the shared sphere table [n_shared][OB_WORDS]
-  int n_shared;
-  const double *own;       // the per-problem table (obstacles.h, bob_index), or null
-  const int *own_counts;   // [B]
-  int own_K;
+  ScoreOperands ops;       // the score's (call_parts.h); not read without out_score
   double *out_score;       // [B][S][4], or null
 };
 
@@ -160,9 +153,10 @@ __global__ __launch_bounds__(CL_BLOCK) void k_closed_loop_scored(ModelConsts<dou
     ex.wrench_step = e.n_w == 1 ? 0 : CL_WRENCH;
   }
   int n_own = 0;
+  const SphereTables &t = e.ops.spheres;
   if constexpr (SCORE) {
     ex.score = (live && e.out_score) ? e.out_score + row * CL_SCORE : nullptr;
-    if (e.own) n_own = e.own_counts[b];
+    if (t.own) n_own = t.own_counts[b];
   }
   auto fly = [&](auto &fetch) {
     using F = std::remove_reference_t<decltype(fetch)>;
@@ -174,17 +168,17 @@ __global__ __launch_bounds__(CL_BLOCK) void k_closed_loop_scored(ModelConsts<dou
     }
   };
   if constexpr (SCORE) {
-    const double *desired = e.desired + (long)b * e.desired_step;
+    const double *desired = e.ops.desired + (long)b * e.ops.desired_step;
     if constexpr (SHARED) {
       __shared__ ClScoreImage image;
-      ex.spheres = ClSpheres{image.shared, e.n_shared, image.own, n_own, 1, OB_BWORDS};
+      ex.spheres = ClSpheres{image.shared, t.n_shared, image.own, n_own, 1, OB_BWORDS};
       ClSharedScoreFetch fetch{reinterpret_cast<const cl_dv2 *>(plan), reinterpret_cast<const cl_dv2 *>(gains), reinterpret_cast<const cl_dv2 *>(desired),
-                               reinterpret_cast<const cl_dv2 *>(e.q), e.q_step / 2, &image, lane, a.i1, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}};
-      fetch.prime(a.i0, e.shared, e.n_shared, e.own, e.own_K, b, n_own);
+                               reinterpret_cast<const cl_dv2 *>(e.ops.q), e.ops.q_step / 2, &image, lane, a.i1, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}};
+      fetch.prime(a.i0, t.shared, t.n_shared, t.own, t.own_K, b, n_own);
       fly(fetch);
     } else {
-      ex.spheres = ClSpheres{e.shared, e.n_shared, e.own ? e.own + bob_index(b, e.own_K, 0, 0) : nullptr, n_own, OB_TILE, OB_BWORDS * OB_TILE};
-      ClFlatScoreFetch fetch{ClFlatFetch{plan, gains}, desired, e.q, (long)e.q_step};
+      ex.spheres = ClSpheres{t.shared, t.n_shared, t.own ? t.own + bob_index(b, t.own_K, 0, 0) : nullptr, n_own, OB_TILE, OB_BWORDS * OB_TILE};
+      ClFlatScoreFetch fetch{ClFlatFetch{plan, gains}, desired, e.ops.q, (long)e.ops.q_step};
       fly(fetch);
     }
   } else if constexpr (SHARED) {

@@ -28,12 +28,13 @@ hipError_t launch_covariance(hipStream_t stream, const ModelConsts<double> &cons
     e = call.integrator == 1 ? build_go<1>(stream, consts, a, grid, call.d_models) : build_go<0>(stream, consts, a, grid, call.d_models);
     if (e != hipSuccess) return e;
   }
-  CovChainArgs ch{call.d_image, call.d_cov, call.d_mean, call.n, call.i0, call.i1, call.k};
+  CovChainArgs ch{call.d_image, call.d_cov, call.d_mean, call.n, call.i0, call.i1, {}};
+  const qilqr_gust_model &g = call.rule.gust;
+  cov_coeffs(call.rule.state_sigma, g.mean, g.sigma, g.tau_force_s, g.tau_torque_s, (call.rule.flags & QILQR_COV_WRENCH_HELD) != 0, consts.dt, ch.k);
   hipLaunchKernelGGL(k_cov_chain, dim3((unsigned)call.B), dim3(COV_BLOCK), 0, stream, ch);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (call.d_summary) {
-    const CovSummaryArgs s{call.d_plan, call.d_gains, call.d_cov, call.d_mean, call.d_summary, call.n, call.i0, call.i1, consts.dt,
-                           call.d_shared, call.n_shared, call.d_own, call.d_own_counts, call.own_K};
+    const CovSummaryArgs s{call.d_plan, call.d_gains, call.d_cov, call.d_mean, call.d_summary, call.n, call.i0, call.i1, consts.dt, call.spheres};
     hipLaunchKernelGGL(k_cov_summary, dim3((unsigned)call.B), dim3(COV_BLOCK), 0, stream, s);
     e = hipGetLastError();
   }

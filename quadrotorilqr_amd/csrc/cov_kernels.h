@@ -32,6 +32,7 @@
 
 #include "backward_layout.h"
 #include "batch_models.h"
+#include "call_parts.h"
 #include "closed_loop_kernels.h"
 #include "cov_launch.h"
 #include "obstacles.h"
@@ -371,11 +372,7 @@ struct CovSummaryArgs {
   double *summary;             // [B][COV_SUMMARY]
   int n, i0, i1;
   double dt;
-  const double *shared;        // the handle's sphere tables, as ClosedLoopScoreArgs holds them
-  int n_shared;
-  const double *own;
-  const int *own_counts;
-  int own_K;
+  SphereTables spheres;        // the handle's (call_parts.h)
 };
 
 #if defined(__HIPCC__)
@@ -517,7 +514,8 @@ __global__ __launch_bounds__(COV_BLOCK) void k_cov_chain(CovChainArgs a) {
 __global__ __launch_bounds__(COV_BLOCK) void k_cov_summary(CovSummaryArgs a) {
   const int lane = threadIdx.x;
   const long b = blockIdx.x, knot0 = b * a.n;
-  ClSpheres sp{a.shared, a.n_shared, a.own ? a.own + bob_index(b, a.own_K, 0, 0) : nullptr, a.own ? a.own_counts[b] : 0, OB_TILE, OB_BWORDS * OB_TILE};
+  const SphereTables &t = a.spheres;
+  ClSpheres sp{t.shared, t.n_shared, t.own ? t.own + bob_index(b, t.own_K, 0, 0) : nullptr, t.own ? t.own_counts[b] : 0, OB_TILE, OB_BWORDS * OB_TILE};
   CovPlanSummary s;
   for (int i = a.i0 + lane; i <= a.i1; i += COV_BLOCK) {
     const double *K = a.gains ? a.gains + (knot0 + i) * 52 + 4 : nullptr;

@@ -89,6 +89,8 @@ inline const char *cov_refusal(const CovCall &c) {
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 
+#include "../../include/quadrotor_ilqr.h"
+#include "call_parts.h"
 #include "se3_math.h"
 
 namespace qilqr {
@@ -104,12 +106,8 @@ struct CovLaunch {
   int B, n, i0, i1;
   int integrator;          // 0 explicit Euler, 1 Runge-Kutta
   const double *d_models;  // the per-problem model records (batch_models.h) of these B plans, or null
-  CovCoeffs k;
-  const double *d_shared;  // the handle's sphere tables
-  int n_shared;
-  const double *d_own;
-  const int *d_own_counts;
-  int own_K;
+  qilqr_cov_rule rule;     // the caller's
+  SphereTables spheres;    // the handle's (call_parts.h)
 };
 // enqueues the two or three launches on `stream` and returns what they returned; nothing is waited for
 __attribute__((visibility("hidden"))) hipError_t launch_covariance(hipStream_t stream, const ModelConsts<double> &consts, const CovLaunch &call);

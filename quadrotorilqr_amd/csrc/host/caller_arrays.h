@@ -3,9 +3,10 @@
 // k_closed_loop_scored: closed_loop.hip, closed_loop_scored.hip), the ends of the Monte-Carlo loop (monte_carlo.hip) and the risk
 // measures and the choice among candidate plans behind it (risk.hip), the sampling planner (mppi.hip, mppi_adapt.hip) and the linear
 // covariance analysis of a plan's closed loop (cov.hip; its rule is cov_launch.h's, its scratch the handle's).  Each call has
-// one refusal (from the rules of ranges.h, closed_loop_launch.h, monte_carlo_launch.h, risk_launch.h, mppi_launch.h and mppi_adapt_launch.h), one enqueue, a device form that enqueues and
-// returns, and -- the shift and the flight -- a host form that stages the arrays through one DeviceScratch.  Part of ilqr_capi.hip's
-// translation unit.
+// one refusal (from the rules of ranges.h and the six *_launch.h), one enqueue, a device form that enqueues and returns (on_device), and
+// -- the shift and the flight -- a host form that stages the arrays through one DeviceScratch (enqueue_and_drain).  What the calls read of
+// the handle for a launch is read in one place each: sphere_tables, score_operands (the records are call_parts.h's).  Part of
+// ilqr_capi.hip's translation unit.
 #pragma once
 
 namespace {
@@ -21,6 +22,43 @@ int enqueue_and_drain(qilqr_solver *s, const char *entry, Enqueue &&enqueue, Cop
   if (e == hipSuccess) e = drained;
   if (e == hipSuccess) e = hipGetLastError();
   if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e));
+  return QILQR_OK;
+}
+
+// A launch's outcome as a return code: a HIP failure is reported under the kernel's name.
+int launched(const char *kernel, hipError_t e) {
+  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(e));
+  return QILQR_OK;
+}
+// The tail of a device form, behind its refusal: the handle's device, then the enqueue (on the handle's stream; not waited for), which
+// reports its own failure -- launched() for the launch, HIP_TRY for operands and scratch made on the way.
+template <typename Enqueue>
+int on_device(qilqr_solver *s, Enqueue &&enqueue) {
+  HIP_TRY(hipSetDevice(s->device));
+  return enqueue();
+}
+
+// ---- what a launch reads of the handle, each in one place (the records are call_parts.h's)
+SphereTables sphere_tables(const qilqr_solver *s) {
+  return SphereTables{s->n_obstacles > 0 ? s->d_obstacles : nullptr, s->n_obstacles, s->pobs_B > 0 ? s->d_pobs : nullptr,
+                      s->pobs_B > 0 ? s->d_pobs_counts : nullptr, s->pobs_K};
+}
+// what a score reads: the desired trajectory (the caller's per plan, or the handle's from its horizon start), the state weights, the tables
+int score_operands(qilqr_solver *s, const double *d_desired, int32_t n, ScoreOperands &o) {
+  o.desired = d_desired ? d_desired : (const double *)s->d_desired + 18 * (size_t)s->k0;
+  o.desired_step = d_desired ? 18l * n : 0;
+  if (s->n_sched > 0) {
+    o.q = s->d_qsched + (size_t)SCHED_WORDS * s->k0;
+    o.q_step = SCHED_WORDS;
+  } else {
+    if (!s->d_cl_q) {  // (Q lies 8 bytes off a 16-byte boundary inside ModelConsts: a copy of its own, made once; the handle's Q never changes)
+      HIP_TRY(hipMalloc((void **)&s->d_cl_q, sizeof(double) * 144));
+      HIP_TRY(hipMemcpyAsync(s->d_cl_q, s->consts.Q, sizeof(double) * 144, hipMemcpyHostToDevice, s->stream));
+    }
+    o.q = s->d_cl_q;
+    o.q_step = 0;
+  }
+  o.spheres = sphere_tables(s);
   return QILQR_OK;
 }
 
@@ -46,9 +84,7 @@ int shift_refuse(const qilqr_solver *s, const double *traj, const double *x0, in
 }
 int shift_enqueue(qilqr_solver *s, const double *d_traj, const double *d_x0, int32_t B, int32_t n, int32_t steps, int32_t tail, double *d_out) {
   const ShiftLaunch call{d_traj, d_x0, d_out, B, n, steps, tail, s->integrator, s->limited ? &s->limits : nullptr, s->modeled ? s->d_models : nullptr};
-  const hipError_t e = launch_shift(s->stream, s->consts, call);
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_shift: ") + hipGetErrorString(e));
-  return QILQR_OK;
+  return launched("k_shift", launch_shift(s->stream, s->consts, call));
 }
 
 // ---- the plan's feedback law flown from given states.  ONE flight: the plain call is the scored call without a wrench, a desired
@@ -76,31 +112,6 @@ int closed_loop_refuse(const qilqr_solver *s, const double *plan, const double *
   if (s && s->modeled && !s->f32 && s->models_B != (long)B * S) text += ": they were set for " + std::to_string(s->models_B) + ", this call has B * S = " + std::to_string((long)B * S);
   return fail(QILQR_ERR_INVALID_ARG, text);
 }
-// what a score reads of the handle, for a launch record `call` that has ClosedLoopScoredLaunch's fields of the score (that one, and
-// MppiLaunch): the desired trajectory (the caller's per plan, or the handle's from its horizon start), the state weights, the two sphere tables
-template <typename Launch>
-int score_operands(qilqr_solver *s, const double *d_desired, int32_t n, Launch &call) {
-  call.d_desired = d_desired ? d_desired : (const double *)s->d_desired + 18 * (size_t)s->k0;
-  call.desired_step = d_desired ? 18l * n : 0;
-  if (s->n_sched > 0) {
-    call.d_q = s->d_qsched + (size_t)SCHED_WORDS * s->k0;
-    call.q_step = SCHED_WORDS;
-  } else {
-    if (!s->d_cl_q) {  // (Q lies 8 bytes off a 16-byte boundary inside ModelConsts: a copy of its own, made once; the handle's Q never changes)
-      HIP_TRY(hipMalloc((void **)&s->d_cl_q, sizeof(double) * 144));
-      HIP_TRY(hipMemcpyAsync(s->d_cl_q, s->consts.Q, sizeof(double) * 144, hipMemcpyHostToDevice, s->stream));
-    }
-    call.d_q = s->d_cl_q;
-    call.q_step = 0;
-  }
-  call.d_shared = s->n_obstacles > 0 ? s->d_obstacles : nullptr;
-  call.n_shared = s->n_obstacles;
-  call.d_own = s->pobs_B > 0 ? s->d_pobs : nullptr;
-  call.d_own_counts = s->pobs_B > 0 ? s->d_pobs_counts : nullptr;
-  call.own_K = s->pobs_K;
-  return QILQR_OK;
-}
-
 int closed_loop_enqueue(qilqr_solver *s, const char *kernel, const double *d_plan, const double *d_gains, const double *d_x0, const double *d_wrench,
                         int32_t n_w, const double *d_desired, int32_t B, int32_t n, int32_t S, int32_t i0, int32_t i1, double *d_out_traj,
                         double *d_out_stats, double *d_out_score) {
@@ -111,10 +122,8 @@ int closed_loop_enqueue(qilqr_solver *s, const char *kernel, const double *d_pla
   call.n_w = n_w;
   call.d_out_score = d_out_score;
   if (d_out_score)
-    if (int rc = score_operands(s, d_desired, n, call)) return rc;
-  const hipError_t e = launch_closed_loop_scored(s->stream, s->consts, call);
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(e));
-  return QILQR_OK;
+    if (int rc = score_operands(s, d_desired, n, call.score)) return rc;
+  return launched(kernel, launch_closed_loop_scored(s->stream, s->consts, call));
 }
 
 int closed_loop_device(qilqr_solver *s, const FlightNames &names, const double *d_plan, const double *d_gains, const double *d_x0, const double *d_wrench,
@@ -122,9 +131,9 @@ int closed_loop_device(qilqr_solver *s, const FlightNames &names, const double *
                        double *d_out_stats, double *d_out_score) {
   int rc = closed_loop_refuse(s, d_plan, d_gains, d_x0, d_wrench, n_w, d_desired, B, n, S, i0, i1, d_out_traj, d_out_stats, d_out_score);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  // (enqueued on the handle's stream; not waited for)
-  return closed_loop_enqueue(s, names.kernel, d_plan, d_gains, d_x0, d_wrench, n_w, d_desired, B, n, S, i0, i1, d_out_traj, d_out_stats, d_out_score);
+  return on_device(s, [&] {
+    return closed_loop_enqueue(s, names.kernel, d_plan, d_gains, d_x0, d_wrench, n_w, d_desired, B, n, S, i0, i1, d_out_traj, d_out_stats, d_out_score);
+  });
 }
 
 int closed_loop_host(qilqr_solver *s, const FlightNames &names, const double *plan, const double *gains, const double *x0, const double *wrench,
@@ -180,8 +189,7 @@ int qilqr_shift_batch_device(qilqr_solver *s, const double *d_traj, const double
                              double *d_out) {
   int rc = shift_refuse(s, d_traj, d_x0, B, n, steps, tail, d_out);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return shift_enqueue(s, d_traj, d_x0, B, n, steps, tail, d_out);  // (enqueued on the handle's stream; not waited for)
+  return on_device(s, [&] { return shift_enqueue(s, d_traj, d_x0, B, n, steps, tail, d_out); });
 }
 
 int qilqr_shift_batch(qilqr_solver *s, const double *traj, const double *x0, int32_t B, int32_t n, int32_t steps, int32_t tail, double *out) {
@@ -251,15 +259,8 @@ int qilqr_sample_gusts_device(qilqr_solver *s, const qilqr_gust_model *m, uint64
     call.sigma[k] = m ? m->sigma[k] : 0.0;
   }
   if (const char *why = sample_gusts_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  SampleGustsLaunch go{d_wrench, B, S, n_w, b0, s0, seed, s->consts.dt, {}, {}, m->tau_force_s, m->tau_torque_s};
-  for (int k = 0; k < 6; ++k) {
-    go.mean[k] = m->mean[k];
-    go.sigma[k] = m->sigma[k];
-  }
-  const hipError_t e = launch_sample_gusts(s->stream, go);  // (enqueued on the handle's stream; not waited for)
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_sample_gusts: ") + hipGetErrorString(e));
-  return QILQR_OK;
+  const SampleGustsLaunch go{d_wrench, B, S, n_w, b0, s0, seed, s->consts.dt, *m};
+  return on_device(s, [&] { return launched("k_sample_gusts", launch_sample_gusts(s->stream, go)); });
 }
 
 int qilqr_sample_states_device(qilqr_solver *s, const double *d_x_nom, const double *sigma12, uint64_t seed, int32_t B, int32_t S, int32_t b0,
@@ -267,21 +268,15 @@ int qilqr_sample_states_device(qilqr_solver *s, const double *d_x_nom, const dou
   SampleStatesCall call{s != nullptr, sigma12 != nullptr, d_x_nom, d_x0, B, S, b0, s0, flags, {}};
   for (int k = 0; k < 12; ++k) call.sigma[k] = sigma12 ? sigma12[k] : 0.0;
   if (const char *why = sample_states_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
   SampleStatesLaunch go{d_x_nom, d_x0, B, S, b0, s0, flags, seed, {}};
   for (int k = 0; k < 12; ++k) go.sigma[k] = sigma12[k];
-  const hipError_t e = launch_sample_states(s->stream, go);  // (not waited for)
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_sample_states: ") + hipGetErrorString(e));
-  return QILQR_OK;
+  return on_device(s, [&] { return launched("k_sample_states", launch_sample_states(s->stream, go)); });
 }
 
 int qilqr_reduce_scores_device(qilqr_solver *s, const double *d_score, int32_t B, int32_t S, double *d_summary) {
   const ReduceScoresCall call{s != nullptr, d_score, d_summary, B, S};
   if (const char *why = reduce_scores_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  const hipError_t e = launch_reduce_scores(s->stream, ReduceScoresLaunch{d_score, d_summary, B, S});  // (not waited for)
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_reduce_scores: ") + hipGetErrorString(e));
-  return QILQR_OK;
+  return on_device(s, [&] { return launched("k_reduce_scores", launch_reduce_scores(s->stream, ReduceScoresLaunch{d_score, d_summary, B, S})); });
 }
 // ---- behind the reduction: tail measures per plan and the choice among a vehicle's candidates (k_risk_scores, k_select_plans and
 // k_gather_plans: risk_kernels.h, compiled by risk.hip).  The handle gives its stream and its device; the rules are risk_launch.h's.
@@ -292,10 +287,8 @@ int qilqr_risk_scores_device(qilqr_solver *s, const double *d_score, int32_t B, 
                              double *d_risk) {
   const RiskScoresCall call{s != nullptr, d_score, d_risk, levels, B, S, column, n_levels};
   if (const char *why = risk_scores_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  const hipError_t e = launch_risk_scores(s->stream, RiskScoresLaunch{d_score, d_risk, B, S, column, n_levels, levels});  // (not waited for)
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_risk_scores: ") + hipGetErrorString(e));
-  return QILQR_OK;
+  const RiskScoresLaunch go{d_score, d_risk, B, S, column, n_levels, levels};
+  return on_device(s, [&] { return launched("k_risk_scores", launch_risk_scores(s->stream, go)); });
 }
 
 int qilqr_select_plans_device(qilqr_solver *s, const double *d_summary, const double *d_risk, int32_t n_levels, const qilqr_select_rule *rule, int32_t V,
@@ -305,13 +298,9 @@ int qilqr_select_plans_device(qilqr_solver *s, const double *d_summary, const do
                              rule ? rule->max_diverged_fraction : 0.0, rule ? rule->min_clearance : 0.0, d_summary, d_risk, d_choice, d_info, d_plan, d_gains,
                              d_out_plan, d_out_gains, n_levels, V, C, n};
   if (const char *why = select_plans_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
   const bool risky = rule->objective >= 2;
-  const SelectPlansLaunch go{d_summary, risky ? d_risk : nullptr, d_choice, d_info, risky ? n_levels : 0, V, C, rule->objective, rule->level,
-                             rule->max_collision_fraction, rule->max_diverged_fraction, rule->min_clearance, d_plan, d_gains, d_out_plan, d_out_gains, n};
-  const hipError_t e = launch_select_plans(s->stream, go);  // (one or two launches; not waited for)
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_select_plans: ") + hipGetErrorString(e));
-  return QILQR_OK;
+  const SelectPlansLaunch go{d_summary, risky ? d_risk : nullptr, d_choice, d_info, risky ? n_levels : 0, V, C, *rule, d_plan, d_gains, d_out_plan, d_out_gains, n};
+  return on_device(s, [&] { return launched("k_select_plans", launch_select_plans(s->stream, go)); });  // (one or two launches)
 }
 }  // extern "C"
 
@@ -344,15 +333,9 @@ MppiCall mppi_call_of(const qilqr_solver *s, bool update, const qilqr_mppi_rule 
 // the launch record of an admitted call
 int mppi_launch_of(qilqr_solver *s, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0, const double *d_desired,
                    double *d_score, int32_t B, int32_t n, int32_t S, int32_t b0, double *d_out_plan, double *d_info, MppiLaunch &go) {
-  go.d_plan = d_plan; go.d_x0 = d_x0; go.d_score = d_score; go.d_out_plan = d_out_plan; go.d_info = d_info;
-  go.B = B; go.n = n; go.S = S; go.b0 = b0;
-  go.seed = seed;
-  for (int a = 0; a < 4; ++a) go.sigma[a] = rule->sigma[a];
-  go.tau_s = rule->tau_s; go.lambda = rule->lambda; go.collision_cost = rule->collision_cost; go.flags = rule->flags;
-  go.integrator = s->integrator;
-  go.limits = s->limited ? &s->limits : nullptr;
-  go.d_models = s->modeled ? s->d_models : nullptr;
-  return score_operands(s, d_desired, n, go);
+  go = MppiLaunch{d_plan, d_x0, d_score, d_out_plan, d_info, B, n, S, b0, seed, *rule, s->integrator, s->limited ? &s->limits : nullptr,
+                  s->modeled ? s->d_models : nullptr, {}};
+  return score_operands(s, d_desired, n, go.score);
 }
 
 int mppi_device(qilqr_solver *s, bool update, const qilqr_mppi_rule *rule, uint64_t seed, const double *d_plan, const double *d_x0, const double *d_desired,
@@ -360,13 +343,11 @@ int mppi_device(qilqr_solver *s, bool update, const qilqr_mppi_rule *rule, uint6
   const MppiCall call = mppi_call_of(s, update, rule, d_plan, d_x0, d_desired, d_score, B, n, S, b0, d_out_plan, d_info);
   bool length = false;
   if (const char *why = mppi_refusal(call, &length)) return fail(length ? QILQR_ERR_LENGTH_MISMATCH : QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  MppiLaunch go{};
-  if (int rc = mppi_launch_of(s, rule, seed, d_plan, d_x0, d_desired, d_score, B, n, S, b0, d_out_plan, d_info, go)) return rc;
-  // (enqueued on the handle's stream; not waited for)
-  const hipError_t e = update ? launch_mppi_update(s->stream, s->consts, go) : launch_mppi_flight(s->stream, s->consts, go);
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string(update ? "k_mppi_update: " : "k_mppi_flight: ") + hipGetErrorString(e));
-  return QILQR_OK;
+  return on_device(s, [&] {
+    MppiLaunch go{};
+    if (int rc = mppi_launch_of(s, rule, seed, d_plan, d_x0, d_desired, d_score, B, n, S, b0, d_out_plan, d_info, go)) return rc;
+    return launched(update ? "k_mppi_update" : "k_mppi_flight", update ? launch_mppi_update(s->stream, s->consts, go) : launch_mppi_flight(s->stream, s->consts, go));
+  });
 }
 
 // the same two calls with the deviations per plan, knot and rotor (k_mppi_flight_spread and k_mppi_adapt: mppi_adapt_kernels.h, compiled
@@ -389,22 +370,15 @@ int mppi_spread_device(qilqr_solver *s, bool adapting, const qilqr_mppi_rule *ru
   call.out_spread = d_out_spread;
   bool length = false;
   if (const char *why = mppi_spread_refusal(call, &length)) return fail(length ? QILQR_ERR_LENGTH_MISMATCH : QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  MppiSpreadLaunch go{};
-  if (int rc = mppi_launch_of(s, rule, seed, d_plan, d_x0, d_desired, d_score, B, n, S, b0, d_out_plan, d_info, go.base)) return rc;
-  go.d_spread = d_spread;
-  go.d_out_spread = d_out_spread;
-  if (adapting) {
-    for (int a = 0; a < 4; ++a) {
-      go.floor[a] = adapt->floor[a];
-      go.cap[a] = adapt->cap[a];
-    }
-    go.rate = adapt->rate;
-  }
-  // (enqueued on the handle's stream; not waited for)
-  const hipError_t e = adapting ? launch_mppi_adapt(s->stream, s->consts, go) : launch_mppi_flight_spread(s->stream, s->consts, go);
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string(adapting ? "k_mppi_adapt: " : "k_mppi_flight_spread: ") + hipGetErrorString(e));
-  return QILQR_OK;
+  return on_device(s, [&] {
+    MppiSpreadLaunch go{};
+    if (int rc = mppi_launch_of(s, rule, seed, d_plan, d_x0, d_desired, d_score, B, n, S, b0, d_out_plan, d_info, go.base)) return rc;
+    go.d_spread = d_spread;
+    go.d_out_spread = d_out_spread;
+    if (adapting) go.adapt = *adapt;
+    return launched(adapting ? "k_mppi_adapt" : "k_mppi_flight_spread",
+                    adapting ? launch_mppi_adapt(s->stream, s->consts, go) : launch_mppi_flight_spread(s->stream, s->consts, go));
+  });
 }
 }  // namespace
 
@@ -479,29 +453,16 @@ int qilqr_covariance_device(qilqr_solver *s, const qilqr_cov_rule *rule, const d
     call.f32 = s->f32; call.modeled = s->modeled; call.models_B = s->models_B; call.pobs_B = s->pobs_B;
   }
   if (const char *why = cov_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
-  HIP_TRY(hipSetDevice(s->device));
-  const size_t knots = (size_t)B * (size_t)n;
-  if (int rc = cov_scratch(s, &s->d_cov_image, &s->cov_image_words, knots * COV_IMAGE, true)) return rc;
-  CovLaunch go{};
-  go.d_plan = d_plan; go.d_gains = d_gains; go.d_image = s->d_cov_image;
-  go.d_cov = d_cov; go.d_mean = d_mean; go.d_summary = d_summary;
-  if (d_summary && (!d_cov || !d_mean)) {  // the summary reads Sigma_i and m_i where the chain left them
-    if (int rc = cov_scratch(s, &s->d_cov_out, &s->cov_out_words, knots * (QILQR_COV + 12), false)) return rc;
-    if (!d_cov) go.d_cov = s->d_cov_out;
-    if (!d_mean) go.d_mean = s->d_cov_out + knots * QILQR_COV;
-  }
-  go.B = B; go.n = n; go.i0 = i0; go.i1 = i1;
-  go.integrator = s->integrator;
-  go.d_models = s->modeled ? s->d_models : nullptr;
-  cov_coeffs(rule->state_sigma, rule->gust.mean, rule->gust.sigma, rule->gust.tau_force_s, rule->gust.tau_torque_s, (rule->flags & QILQR_COV_WRENCH_HELD) != 0,
-             s->consts.dt, go.k);
-  go.d_shared = s->n_obstacles > 0 ? s->d_obstacles : nullptr;
-  go.n_shared = s->n_obstacles;
-  go.d_own = s->pobs_B > 0 ? s->d_pobs : nullptr;
-  go.d_own_counts = s->pobs_B > 0 ? s->d_pobs_counts : nullptr;
-  go.own_K = s->pobs_K;
-  const hipError_t e = launch_covariance(s->stream, s->consts, go);  // (enqueued on the handle's stream; not waited for)
-  if (e != hipSuccess) return fail(QILQR_ERR_HIP, std::string("k_cov_chain: ") + hipGetErrorString(e));
-  return QILQR_OK;
+  return on_device(s, [&] {
+    const size_t knots = (size_t)B * (size_t)n;
+    if (int rc = cov_scratch(s, &s->d_cov_image, &s->cov_image_words, knots * COV_IMAGE, true)) return rc;
+    CovLaunch go{d_plan, d_gains, s->d_cov_image, d_cov, d_mean, d_summary, B, n, i0, i1, s->integrator, s->modeled ? s->d_models : nullptr, *rule, sphere_tables(s)};
+    if (d_summary && (!d_cov || !d_mean)) {  // the summary reads Sigma_i and m_i where the chain left them
+      if (int rc = cov_scratch(s, &s->d_cov_out, &s->cov_out_words, knots * (QILQR_COV + 12), false)) return rc;
+      if (!d_cov) go.d_cov = s->d_cov_out;
+      if (!d_mean) go.d_mean = s->d_cov_out + knots * QILQR_COV;
+    }
+    return launched("k_cov_chain", launch_covariance(s->stream, s->consts, go));
+  });
 }
 }  // extern "C"

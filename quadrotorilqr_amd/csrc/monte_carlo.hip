@@ -11,7 +11,7 @@ namespace qilqr {
 
 hipError_t launch_sample_gusts(hipStream_t stream, const SampleGustsLaunch &call) {
   SampleGustsArgs a{call.d_wrench, call.B, call.S, call.n_w, (uint32_t)call.b0, (uint32_t)call.s0, call.seed, {}};
-  gust_coeffs(call.mean, call.sigma, call.tau_force_s, call.tau_torque_s, call.dt, a.m);
+  gust_coeffs(call.model.mean, call.model.sigma, call.model.tau_force_s, call.model.tau_torque_s, call.dt, a.m);
   const long blocks = ((long)call.B * call.S + MC_GUST_FLIGHTS - 1) / MC_GUST_FLIGHTS;
   if (blocks > 0x7fffffffl) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_sample_gusts, dim3((unsigned)blocks), dim3(MC_GUST_BLOCK), 0, stream, a);

@@ -84,6 +84,8 @@ inline const char *reduce_scores_refusal(const ReduceScoresCall &c) {
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 
+#include "../../include/quadrotor_ilqr.h"
+
 namespace qilqr {
 
 struct SampleGustsLaunch {
@@ -91,7 +93,7 @@ struct SampleGustsLaunch {
   int B, S, n_w, b0, s0;
   uint64_t seed;
   double dt;         // the handle's
-  double mean[6], sigma[6], tau_force_s, tau_torque_s;
+  qilqr_gust_model model;  // the caller's
 };
 struct SampleStatesLaunch {
   const double *d_x_nom;  // [B][13], device

@@ -28,7 +28,7 @@ hipError_t flight(hipStream_t stream, const ModelConsts<double> &c, const MppiLa
   const long blocks = mppi_flight_blocks(call.B, S);
   if (blocks <= 0) return hipErrorInvalidValue;
   MppiFlightArgs a = mppi_flight_args(call, plan, S, score, score_step, nominal, traj);
-  mppi_coeffs(call.sigma, call.tau_s, c.dt, a.m);
+  mppi_coeffs(call.rule.sigma, call.rule.tau_s, c.dt, a.m);
   return call.integrator == 1 ? flight_go<1>(stream, c, a, dim3((unsigned)blocks), call) : flight_go<0>(stream, c, a, dim3((unsigned)blocks), call);
 }
 }  // namespace
@@ -40,7 +40,7 @@ hipError_t launch_mppi_flight(hipStream_t stream, const ModelConsts<double> &con
 hipError_t launch_mppi_update(hipStream_t stream, const ModelConsts<double> &consts, const MppiLaunch &call) {
   if (call.S > MPPI_MAX_SAMPLES) return hipErrorInvalidValue;
   MppiCoeffs m;
-  mppi_coeffs(call.sigma, call.tau_s, consts.dt, m);
+  mppi_coeffs(call.rule.sigma, call.rule.tau_s, consts.dt, m);
   const MppiUpdateArgs a = mppi_update_args(call, m);
   with_update_lanes(call.S, [&](auto lanes) {
     hipLaunchKernelGGL(k_mppi_update<decltype(lanes)::value>, dim3((unsigned)call.B), dim3(decltype(lanes)::value), 0, stream, a);

@@ -27,7 +27,7 @@ hipError_t launch_mppi_flight_spread(hipStream_t stream, const ModelConsts<doubl
   if (blocks <= 0) return hipErrorInvalidValue;
   MppiFlightSpreadArgs a{};
   a.f = mppi_flight_args(m, m.d_plan, m.S, m.d_score, 4l * m.S, false, nullptr);
-  mppi_unit_coeffs(m.tau_s, consts.dt, a.f.m);
+  mppi_unit_coeffs(m.rule.tau_s, consts.dt, a.f.m);
   a.spread = call.d_spread;
   return m.integrator == 1 ? flight_go<1>(stream, consts, a, dim3((unsigned)blocks), m) : flight_go<0>(stream, consts, a, dim3((unsigned)blocks), m);
 }
@@ -37,11 +37,11 @@ hipError_t launch_mppi_adapt(hipStream_t stream, const ModelConsts<double> &cons
   if (m.S > MPPI_MAX_SAMPLES) return hipErrorInvalidValue;
   MppiAdaptArgs a{};
   MppiCoeffs unit;
-  mppi_unit_coeffs(m.tau_s, consts.dt, unit);
+  mppi_unit_coeffs(m.rule.tau_s, consts.dt, unit);
   a.u = mppi_update_args(m, unit);
   a.spread = call.d_spread;
   a.out_spread = call.d_out_spread;
-  mppi_adapt_coeffs(call.floor, call.cap, call.rate, a.k);
+  mppi_adapt_coeffs(call.adapt.floor, call.adapt.cap, call.adapt.rate, a.k);
   with_update_lanes(m.S, [&](auto lanes) {
     hipLaunchKernelGGL(k_mppi_adapt<decltype(lanes)::value>, dim3((unsigned)m.B), dim3(decltype(lanes)::value), 0, stream, a);
   });

@@ -68,12 +68,12 @@ inline const char *mppi_spread_refusal(const MppiSpreadCall &c, bool *length) {
 #if defined(__HIPCC__)
 namespace qilqr {
 
-// one call's launch record: MppiLaunch (base.sigma is not read: the draws are the unit recursion's) and the spread
+// one call's launch record: MppiLaunch (base.rule.sigma is not read: the draws are the unit recursion's) and the spread
 struct MppiSpreadLaunch {
   MppiLaunch base;
-  const double *d_spread;   // [B][n][4]
-  double *d_out_spread;     // [B][n][4], or null (the adaptation)
-  double floor[4], cap[4], rate;
+  const double *d_spread;       // [B][n][4]
+  double *d_out_spread;         // [B][n][4], or null (the adaptation)
+  qilqr_mppi_adapt_rule adapt;  // the caller's (the adaptation)
 };
 
 // each enqueues its launches on `stream` and returns what they returned; nothing is waited for.  The adaptation is two launches:

@@ -37,6 +37,7 @@
 #include <stdint.h>
 
 #include "closed_loop_kernels.h"
+#include "mppi_launch.h"
 #include "philox.h"
 
 namespace qilqr {
@@ -283,15 +284,7 @@ struct MppiFlightArgs {
   const double *plan;      // [B][n][18]
   const double *x0;        // sample (b, j) starts at x0 + b * x0_step: [B][13] (13), or words 1..13 of the plan's knot 0 (plan + 1; n * 18)
   long x0_step;
-  const double *desired;   // knot i of plan b is desired + b * desired_step + i * 18
-  long desired_step;       // n * 18 (one per plan), or 0 (the handle's, from its horizon start)
-  const double *q;         // knot i's state weights are q + i * q_step
-  int q_step;              // 144 (a schedule, from the horizon start), or 0 (the handle's Q)
-  const double *shared;    // the shared sphere table [n_shared][OB_WORDS]
-  int n_shared;
-  const double *own;       // the per-problem table (obstacles.h, bob_index), or null
-  const int *own_counts;   // [B]
-  int own_K;
+  ScoreOperands ops;       // the score's (call_parts.h)
   double *score;           // sample (b, j)'s four words are score + b * score_step + 4 j
   long score_step;         // 4 S; the nominal flight of the update: 8, into words 4 .. 7 of info
   double *traj;            // [B][n][18], or null (usually): sample 0's flight is stored -- the S = 1 launch of the update
@@ -301,23 +294,13 @@ struct MppiFlightArgs {
   uint64_t seed;
   MppiCoeffs m;
 };
-// (host) the arguments of a flight of S samples per plan over `plan` from a launch record with MppiLaunch's fields (mppi_launch.h); the
-// coefficients are the caller's to fill
-template <typename Launch>
-inline MppiFlightArgs mppi_flight_args(const Launch &call, const double *plan, int S, double *score, long score_step, bool nominal, double *traj) {
+// (host) the arguments of a flight of S samples per plan over `plan` from a call's launch record; the coefficients are the caller's to fill
+inline MppiFlightArgs mppi_flight_args(const MppiLaunch &call, const double *plan, int S, double *score, long score_step, bool nominal, double *traj) {
   MppiFlightArgs a{};
   a.plan = plan;
   a.x0 = call.d_x0 ? call.d_x0 : call.d_plan + 1;
   a.x0_step = call.d_x0 ? CL_STATE : 18l * call.n;
-  a.desired = call.d_desired;
-  a.desired_step = call.desired_step;
-  a.q = call.d_q;
-  a.q_step = call.q_step;
-  a.shared = call.d_shared;
-  a.n_shared = call.n_shared;
-  a.own = call.d_own;
-  a.own_counts = call.d_own_counts;
-  a.own_K = call.own_K;
+  a.ops = call.score;
   a.score = score;
   a.score_step = score_step;
   a.traj = traj;
@@ -325,7 +308,7 @@ inline MppiFlightArgs mppi_flight_args(const Launch &call, const double *plan, i
   a.n = call.n;
   a.S = S;
   a.b0 = (uint32_t)call.b0;
-  a.flags = call.flags;
+  a.flags = call.rule.flags;
   a.all_nominal = nominal ? 1 : 0;
   a.seed = call.seed;
   return a;
@@ -423,8 +406,9 @@ __device__ __forceinline__ void mppi_flight_block(const ModelConsts<double> &c, 
     lo = L.lo;
     hi = L.hi;
   }
-  const double *plan = a.plan + (long)b * a.n * 18, *desired = a.desired + (long)b * a.desired_step;
-  const int n_own = a.own ? a.own_counts[b] : 0;
+  const double *plan = a.plan + (long)b * a.n * 18, *desired = a.ops.desired + (long)b * a.ops.desired_step;
+  const SphereTables &t = a.ops.spheres;
+  const int n_own = t.own ? t.own_counts[b] : 0;
   MppiSample s;
   s.x0 = a.x0 + (long)b * a.x0_step;
   s.n = a.n;
@@ -432,13 +416,13 @@ __device__ __forceinline__ void mppi_flight_block(const ModelConsts<double> &c, 
   s.plan = a.b0 + (uint32_t)b;
   s.sample = (uint32_t)j;
   s.nominal = a.all_nominal != 0 || mppi_is_nominal(a.flags, j);
-  s.spheres = ClSpheres{image.shared, a.n_shared, image.own, n_own, 1, OB_BWORDS};
+  s.spheres = ClSpheres{image.shared, t.n_shared, image.own, n_own, 1, OB_BWORDS};
   s.score = live ? a.score + (long)b * a.score_step + 4 * (long)j : nullptr;
   s.traj = (TRAJ && live && j == 0 && a.traj) ? a.traj + (long)b * a.n * 18 : nullptr;
-  auto fetch = wrap(MppiSharedFetch{reinterpret_cast<const cl_dv2 *>(plan), reinterpret_cast<const cl_dv2 *>(desired), reinterpret_cast<const cl_dv2 *>(a.q),
-                                    a.q_step / 2, &image, lane, a.n - 1, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}},
+  auto fetch = wrap(MppiSharedFetch{reinterpret_cast<const cl_dv2 *>(plan), reinterpret_cast<const cl_dv2 *>(desired), reinterpret_cast<const cl_dv2 *>(a.ops.q),
+                                    a.ops.q_step / 2, &image, lane, a.n - 1, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}, cl_dv2{0.0, 0.0}},
                     b);
-  fetch.prime(a.shared, a.n_shared, a.own, a.own_K, b, n_own);
+  fetch.prime(t.shared, t.n_shared, t.own, t.own_K, b, n_own);
   if constexpr (MOD) {
     const ModelConsts<double> cm = problem_model(c, pack_get<BatchModels>(lim...), (long)b);
     mppi_sample<INTEG, LIM>(cm, a.m, fetch, s, lo, hi);
@@ -472,9 +456,8 @@ struct MppiUpdateArgs {
   double lim_lo[4], lim_hi[4];
 };
 
-// (host) the arguments of an update from a launch record with MppiLaunch's fields (mppi_launch.h) and the recursion's coefficients
-template <typename Launch>
-inline MppiUpdateArgs mppi_update_args(const Launch &call, const MppiCoeffs &m) {
+// (host) the arguments of an update from a call's launch record and the recursion's coefficients
+inline MppiUpdateArgs mppi_update_args(const MppiLaunch &call, const MppiCoeffs &m) {
   MppiUpdateArgs a{};
   a.plan = call.d_plan;
   a.score = call.d_score;
@@ -483,10 +466,10 @@ inline MppiUpdateArgs mppi_update_args(const Launch &call, const MppiCoeffs &m) 
   a.n = call.n;
   a.S = call.S;
   a.b0 = (uint32_t)call.b0;
-  a.flags = call.flags;
+  a.flags = call.rule.flags;
   a.seed = call.seed;
-  a.lambda = call.lambda;
-  a.collision_cost = call.collision_cost;
+  a.lambda = call.rule.lambda;
+  a.collision_cost = call.rule.collision_cost;
   a.m = m;
   a.limited = call.limits ? 1 : 0;
   for (int r = 0; r < 4; ++r) {

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "call_parts.h"
 #include "ranges.h"
 
 namespace qilqr {
@@ -107,11 +108,11 @@ inline const char *mppi_refusal(const MppiCall &c, bool *length) {
   if (c.f32) return "mppi: needs precision 0 (fp64)";
   if (c.modeled && c.models_B != c.B) return "mppi: the per-problem models must have been set for B plans (plan b flies with model b)";
   if (c.pobs_B > 0 && c.pobs_B != c.B) return "mppi: the per-problem obstacles were set for another B than this call's (the score reads row b of that table)";
-  if (!c.desired && c.n - 1 >= c.n_desired - c.k0) {
+  if (!c.desired && beyond_desired(c.n - 1, c.n_desired, c.k0)) {
     *length = true;
     return "mppi: the scored knots reach beyond the handle's desired trajectory";
   }
-  if (c.n_sched > 0 && c.n - 1 >= c.n_sched - c.k0) {
+  if (beyond_schedule(c.n - 1, c.n_sched, c.k0)) {
     *length = true;
     return "mppi: the scored knots reach beyond the state-weight schedule";
   }
@@ -123,6 +124,7 @@ inline const char *mppi_refusal(const MppiCall &c, bool *length) {
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 
+#include "../../include/quadrotor_ilqr.h"
 #include "box_qp.h"
 #include "se3_math.h"
 
@@ -137,21 +139,11 @@ struct MppiLaunch {
   double *d_info;           // [B][8] (update)
   int B, n, S, b0;
   uint64_t seed;
-  double sigma[4], tau_s, lambda, collision_cost;
-  uint32_t flags;
+  qilqr_mppi_rule rule;          // the caller's
   int integrator;                // 0 explicit Euler, 1 Runge-Kutta
   const ControlLimits *limits;   // the handle's thrust limits, or null
   const double *d_models;        // the per-problem model records (batch_models.h) of these B plans, or null
-  // the score's operands, as ClosedLoopScoredLaunch holds them
-  const double *d_desired;
-  long desired_step;
-  const double *d_q;
-  int q_step;
-  const double *d_shared;
-  int n_shared;
-  const double *d_own;
-  const int *d_own_counts;
-  int own_K;
+  ScoreOperands score;           // from the plan's first knot (call_parts.h)
 };
 
 // each enqueues its launches on `stream` and returns what they returned; nothing is waited for.  The update is two launches:

@@ -32,7 +32,7 @@ hipError_t launch_risk_scores(hipStream_t stream, const RiskScoresLaunch &call) 
 
 hipError_t launch_select_plans(hipStream_t stream, const SelectPlansLaunch &call) {
   const SelectPlansArgs a{call.d_summary, call.d_risk, call.d_choice, call.d_info, call.n_levels, call.V, call.C,
-                          SelectRule{call.objective, call.level, call.max_collision_fraction, call.max_diverged_fraction, call.min_clearance}};
+                          SelectRule{call.rule.objective, call.rule.level, call.rule.max_collision_fraction, call.rule.max_diverged_fraction, call.rule.min_clearance}};
   hipLaunchKernelGGL(k_select_plans, dim3((unsigned)((call.V + 63) / 64)), dim3(64), 0, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !call.d_out_plan) return e;

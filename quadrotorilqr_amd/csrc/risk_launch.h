@@ -80,6 +80,8 @@ inline const char *select_plans_refusal(const SelectPlansCall &c) {
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 
+#include "../../include/quadrotor_ilqr.h"
+
 namespace qilqr {
 
 struct RiskScoresLaunch {
@@ -93,8 +95,7 @@ struct SelectPlansLaunch {
   int32_t *d_choice;                 // [V], device
   double *d_info;                    // [V][4], device
   int n_levels, V, C;
-  int32_t objective, level;
-  double max_collision_fraction, max_diverged_fraction, min_clearance;
+  qilqr_select_rule rule;            // the caller's
   const double *d_plan, *d_gains;    // the gather's (all null: no second launch)
   double *d_out_plan, *d_out_gains;
   int n;

@@ -756,6 +756,80 @@ typedef struct {
 int qilqr_covariance_device(qilqr_solver *s, const qilqr_cov_rule *rule, const double *d_plan, const double *d_gains, int32_t B, int32_t n,
                             int32_t i0, int32_t i1, double *d_cov, double *d_mean, double *d_summary);
 
+/* The device-side twin of qilqr_set_batch_obstacles (extension): a per-problem sphere table that was MADE on the device -- by
+ * qilqr_fleet_neighbours_device below, or by the caller's own kernels -- put into the handle without the host.  d_spheres is
+ * B x K x QILQR_OBSTACLE_WORDS doubles in device memory, the host setter's layout; d_counts is int32[B] in device memory, or NULL for
+ * all K; d_dropped is NULL or one int32 in device memory.
+ * ENQUEUES on the handle's stream and returns; it is not waited for, as every _device call here (the ordering rules of
+ * qilqr_closed_loop_device).  The handle's table and counts are kept and reused while they are large enough, and grow -- with one wait
+ * for the stream -- at the call that needs more: a tick costs one small launch (k_bob_set; and a 4-byte memset for d_dropped) and no
+ * allocation.  qilqr_set_batch_obstacles, the clear included, behaves as before and gives the memory back.
+ * THE ROWS.  What the host setter refuses of the values cannot be looked at without a wait, so the kernel applies it as a rule: per
+ * problem the count is clamped to 0 ... K; a used row with a non-finite word, radius <= 0 or weight < 0 is DROPPED; the rows kept stay
+ * in order and move up, the count becomes the number kept, and the number of rows dropped over the batch goes to *d_dropped.  The table
+ * is written in the tiled device layout with zeros in the rows at or beyond a count and in the padding of the last tile: for a table
+ * whose used rows all pass (and whose other rows are zeros) its bytes are those the host setter uploads.
+ * THE HANDLE is then in the state qilqr_set_batch_obstacles(B, K) leaves: the route, persistent = 1 refused, every call that evaluates
+ * the cost refused for another B, scored flights, the planner and the covariance summary read the table as they read a host-set one.
+ * The largest count and whether a sphere moves are unknown to the host: qilqr_describe says "set on the device" in their place.
+ * QILQR_ERR_INVALID_ARG, before the device is touched, in this order: a NULL handle or d_spheres; B not positive; K outside
+ * 1 ... QILQR_MAX_OBSTACLES; d_spheres off a 16-byte boundary, d_counts or d_dropped off a 4-byte one; a mixed-precision handle. */
+int qilqr_set_batch_obstacles_device(qilqr_solver *s, const double *d_spheres, const int32_t *d_counts, int32_t B, int32_t K,
+                                     int32_t *d_dropped);
+
+/* Fleet deconfliction on the device (extension): who is near whom over the horizon, and each near partner as the moving sphere
+ * qilqr_set_batch_obstacles[_device] takes.  Device arrays only; sharded handles have no such call (use a shard's solver).
+ *
+ * d_plan is B x n x 18: plans in ONE world frame on ONE time base -- knot i of every plan is the same instant t_i = i dt (dt the
+ * handle's).  Rows b with equal b / V form a fleet (V divides B; V = B: one fleet), and only the vehicles of one fleet interact.
+ * THE PAIR.  For ego a and partner b != a of its fleet, at knot i: e = p_a,i - p_b,i per axis (the position is words 1..3 of a knot)
+ * and d2 = fma(ez, ez, fma(ey, ey, ex ex)); the pair's value is the smallest d2 over the knots, taken by strict < from +inf (the first
+ * knot wins a tie; a comparison with a NaN is false), with its knot.  A pair without a finite d2 has d2 = +inf and knot -1 and is
+ * never a neighbour.
+ * THE LIST.  The candidates of ego a are its partners -- under QILQR_FLEET_YIELD_TO_LOWER only those in a smaller row (prioritised
+ * planning: vehicle 0 of a fleet yields to nobody).  The list is the min(K, candidates) candidates smallest in the total order (d2,
+ * partner row), in that order; it does not depend on how the kernels cut the partners into chunks.  K <= QILQR_FLEET_MAX_NEIGHBOURS.
+ * The neighbours are the leading list entries with d2 < range^2 (the square rounded once; distances are compared as squares, with
+ * `conflict` too).
+ * THE LINE of a vehicle, once per vehicle, per axis, sequentially over the knots: pbar = (sum_i p_i) / n, tbar = (n - 1) dt / 2,
+ * Stt = dt^2 n (n^2 - 1) / 12, v = (sum_i fma(t_i - tbar, p_i - pbar, .)) / Stt, c = fma(-tbar, v, pbar) (n = 1: v = 0, c = p_0), and
+ * the residual max_i |p_i - fma(t_i, v, c)| (Euclidean; NaN for a line with a word that is not finite).  fma(t_i, v, c) is where a
+ * per-problem sphere {c, v} stands at knot i.
+ *
+ * Any output may be NULL, but not all of them; each has the bits it has among the others.
+ *   d_nbr      B x K x QILQR_FLEET_NBR: per list entry {partner row in the batch, sqrt(d2), its knot, the partner's residual}; an empty
+ *              entry is {-1, +inf, -1, 0}.
+ *   d_spheres  B x K x QILQR_OBSTACLE_WORDS: per neighbour, in the list's order, {c, v, rule->radius (+ the partner's residual under
+ *              QILQR_FLEET_COVER), rule->weight}.  A partner whose line is not finite becomes no sphere and is skipped; rows at and
+ *              beyond the count are zeros.
+ *   d_counts   int32[B]: the spheres written for row b.
+ *   d_summary  B x QILQR_FLEET_SUMMARY, over ALL partners of the fleet, whatever the yield flag:
+ *     0  the smallest distance (+inf: no partner at a finite one)     3  the partners with d2 < conflict^2
+ *     1  its knot (-1: none)                                          4  d_counts[b]
+ *     2  its partner's row (ties: the smaller row; -1: none)          5  the largest radius written (0: none)      6, 7  zero
+ *
+ * ENQUEUES three launches on the handle's stream (the lines and a staged copy of the positions; all pairs; the merge and the outputs)
+ * and does not drain it, with the ordering rules of qilqr_closed_loop_device; scratch the handle owns grows at the call that needs
+ * more.  QILQR_ERR_INVALID_ARG, before the device is touched, in this order: a NULL rule or d_plan; every output NULL; B, n or V not
+ * positive, or V not dividing B; K outside 1 ... QILQR_FLEET_MAX_NEIGHBOURS; a rule field out of its range, unknown flag bits or
+ * reserved != 0; an array off a 16-byte boundary (d_counts: 4-byte); an output overlapping the plan or another output; a NULL handle,
+ * a mixed-precision one. */
+#define QILQR_FLEET_MAX_NEIGHBOURS 16
+#define QILQR_FLEET_NBR 4
+#define QILQR_FLEET_SUMMARY 8
+#define QILQR_FLEET_COVER 1u
+#define QILQR_FLEET_YIELD_TO_LOWER 2u
+typedef struct qilqr_fleet_rule {
+  double radius;     /* centre-to-centre distance to keep: the radius of the sphere a neighbour becomes; finite, > 0 */
+  double weight;     /* that sphere's weight; finite, >= 0 */
+  double range;      /* a partner becomes a sphere only if its smallest distance over the horizon is < range; > 0, +inf allowed */
+  double conflict;   /* partners whose smallest distance is < conflict are counted in the summary; finite, >= 0 */
+  uint32_t flags;    /* QILQR_FLEET_COVER | QILQR_FLEET_YIELD_TO_LOWER */
+  uint32_t reserved; /* 0 */
+} qilqr_fleet_rule;  /* 40 bytes */
+int qilqr_fleet_neighbours_device(qilqr_solver *s, const qilqr_fleet_rule *rule, const double *d_plan, int32_t B, int32_t n, int32_t V,
+                                  int32_t K, double *d_summary, double *d_nbr, double *d_spheres, int32_t *d_counts);
+
 /* device the solver is bound to, and the HIP stream it launches on (hipStream_t as void*) */
 int qilqr_device(const qilqr_solver *s);
 void *qilqr_stream(const qilqr_solver *s);
@@ -906,8 +980,9 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap);
  * qilqr_select_rule, QILQR_MC_RISK, QILQR_RISK_MAX_LEVELS, QILQR_RISK_MAX_SAMPLES, QILQR_RISK_COST, QILQR_RISK_CLEARANCE,
  * QILQR_SELECT_INFO, qilqr_mppi_flight_device, qilqr_mppi_update_device, qilqr_mppi_rule, QILQR_MPPI_INFO,
  * QILQR_MPPI_FIRST_IS_NOMINAL, qilqr_mppi_flight_spread_device, qilqr_mppi_adapt_device, qilqr_mppi_adapt_rule, qilqr_covariance_device,
- * qilqr_cov_rule, QILQR_COV, QILQR_COV_SUMMARY, QILQR_COV_WRENCH_HELD, qilqr_round_launches and QILQR_ROUND_KERNELS were added within
- * version 7: no structure changed. */
+ * qilqr_cov_rule, QILQR_COV, QILQR_COV_SUMMARY, QILQR_COV_WRENCH_HELD, qilqr_round_launches, QILQR_ROUND_KERNELS,
+ * qilqr_set_batch_obstacles_device, qilqr_fleet_neighbours_device, qilqr_fleet_rule, QILQR_FLEET_MAX_NEIGHBOURS, QILQR_FLEET_NBR,
+ * QILQR_FLEET_SUMMARY, QILQR_FLEET_COVER and QILQR_FLEET_YIELD_TO_LOWER were added within version 7: no structure changed. */
 #define QILQR_ABI_VERSION 7
 int qilqr_abi_version(void);
 

@@ -50,6 +50,10 @@ MPPI_FIRST_IS_NOMINAL = 1  # QILQR_MPPI_FIRST_IS_NOMINAL: qilqr_mppi_rule.flags,
 COV = 144  # QILQR_COV: a knot's covariance, 12 x 12 row-major over the tangent [rho, theta, dv, dw] (covariance_device)
 COV_SUMMARY = 8  # QILQR_COV_SUMMARY: max sqrt(tr P), its knot, sqrt(tr P) at the last knot, max rotation deviation, smallest clearance z, its knot, its sphere, max control deviation
 COV_WRENCH_HELD = 1  # QILQR_COV_WRENCH_HELD: qilqr_cov_rule.flags, one wrench per flight
+FLEET_MAX_NEIGHBOURS = 16  # QILQR_FLEET_MAX_NEIGHBOURS: the K of fleet_neighbours_device
+FLEET_NBR = 4  # QILQR_FLEET_NBR: per list entry the partner's row, the smallest distance over the horizon, its knot, the partner's fit residual
+FLEET_SUMMARY = 8  # QILQR_FLEET_SUMMARY: smallest distance, its knot, its partner, partners in conflict, spheres written, largest radius written, 0, 0
+FLEET_COVER, FLEET_YIELD_TO_LOWER = 1, 2  # QILQR_FLEET_COVER, QILQR_FLEET_YIELD_TO_LOWER: qilqr_fleet_rule.flags
 ROUND_KERNELS = 15  # QILQR_ROUND_KERNELS: the k_round instantiations (round_launches)
 CL_STATS = 4  # QILQR_CL_STATS: max position error, max rotation error, |dx| at the last knot, clamped (knot, rotor) pairs (closed_loop)
 
@@ -67,7 +71,7 @@ EXPORTS = (
     "qilqr_sample_gusts_device", "qilqr_sample_states_device", "qilqr_reduce_scores_device",
     "qilqr_risk_scores_device", "qilqr_select_plans_device",
     "qilqr_mppi_flight_device", "qilqr_mppi_update_device", "qilqr_mppi_flight_spread_device", "qilqr_mppi_adapt_device",
-    "qilqr_covariance_device",
+    "qilqr_covariance_device", "qilqr_set_batch_obstacles_device", "qilqr_fleet_neighbours_device",
     "qilqr_device", "qilqr_stream", "qilqr_stream_wait_event", "qilqr_host_alloc", "qilqr_host_free",
     "qilqr_sharded_create", "qilqr_sharded_create_sized", "qilqr_sharded_create_mask", "qilqr_sharded_create_mask_sized", "qilqr_sharded_destroy", "qilqr_sharded_count", "qilqr_sharded_solver",
     "qilqr_shard_range", "qilqr_solve_batch_sharded",
@@ -115,6 +119,11 @@ class MppiAdaptRule(C.Structure):
 
 class CovRule(C.Structure):
     _fields_ = [("state_sigma", C.c_double * 12), ("gust", GustModel), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FleetRule(C.Structure):
+    _fields_ = [("radius", C.c_double), ("weight", C.c_double), ("range", C.c_double), ("conflict", C.c_double), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class Profile(C.Structure):
@@ -179,6 +188,8 @@ def load():
         lib.qilqr_mppi_flight_spread_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
         lib.qilqr_mppi_adapt_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 3
         lib.qilqr_covariance_device.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p] * 3
+        lib.qilqr_set_batch_obstacles_device.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p]
+        lib.qilqr_fleet_neighbours_device.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 4
         _lib = lib
     return _lib
 
@@ -383,6 +394,14 @@ def cov_rule(state_sigma, gust=None, wrench_held=False):
     elif not isinstance(gust, GustModel):
         gust = gust_model(**gust)
     return CovRule((C.c_double * 12)(*sig), gust, COV_WRENCH_HELD if wrench_held else 0, 0)
+
+
+def fleet_rule(radius, weight, range=np.inf, conflict=None, cover=False, yield_to_lower=False):
+    """a qilqr_fleet_rule: a neighbour becomes a sphere of `radius` (plus its fit residual with cover=True) and `weight` if its smallest
+    distance over the horizon is below `range`; partners closer than `conflict` (None: radius) are counted in the summary;
+    yield_to_lower: only partners in a smaller row are candidates (QILQR_FLEET_YIELD_TO_LOWER)"""
+    return FleetRule(float(radius), float(weight), float(range), float(radius if conflict is None else conflict),
+                     (FLEET_COVER if cover else 0) | (FLEET_YIELD_TO_LOWER if yield_to_lower else 0), 0)
 
 
 def _tail(tail):
@@ -977,6 +996,43 @@ class QuadrotorILQRBatch:
         vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
         _check(load().qilqr_covariance_device(self._h, C.byref(rule), vp(plan), vp(gains), C.c_int32(B), C.c_int32(n), C.c_int32(int(i0)), C.c_int32(i1),
                                               vp(cov), vp(mean), vp(summary)))
+
+    # ---- fleet deconfliction: neighbours of every vehicle as moving spheres, and the per-problem table set from the device
+    def fleet_neighbours_device(self, plan, V, K, radius, weight, range=np.inf, conflict=None, cover=False, yield_to_lower=False, summary=None,
+                                nbr=None, spheres=None, counts=None, wait_current_stream=True):
+        """qilqr_fleet_neighbours_device on torch tensors: plan (B, n, 18) holds plans in one world frame on one time base; rows b with equal
+        b // V form a fleet.  Per vehicle the min(K, candidates) partners of its fleet with the smallest distance over the horizon, in the
+        order (distance, row), and each one closer than `range` as the constant-velocity sphere {c, v, radius, weight} of
+        set_batch_obstacles_device (fleet_rule's arguments).  Outputs, any but not all None: summary (B, 8); nbr (B, K, 4); spheres
+        (B, K, 8); counts int32 (B).  float64, contiguous, on the solver's device.  ENQUEUED on the solver's own stream and not waited for,
+        as closed_loop_device."""
+        if plan is None or plan.dim() != 3 or plan.shape[2] != KNOT:
+            raise TypeError("plan must be (B, n, 18)")
+        import torch
+        B, n, V, K = int(plan.shape[0]), int(plan.shape[1]), int(V), int(K)
+        self._device_tensors(((plan, "plan", (B, n, KNOT)), (summary, "summary", (B, FLEET_SUMMARY)), (nbr, "nbr", (B, K, FLEET_NBR)),
+                              (spheres, "spheres", (B, K, 8)), (counts, "counts", (B,), torch.int32)))
+        rule = fleet_rule(radius, weight, range, conflict, cover, yield_to_lower)
+        if wait_current_stream:
+            self._wait_current_stream(plan)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        _check(load().qilqr_fleet_neighbours_device(self._h, C.byref(rule), vp(plan), C.c_int32(B), C.c_int32(n), C.c_int32(V), C.c_int32(K), vp(summary),
+                                                    vp(nbr), vp(spheres), vp(counts)))
+
+    def set_batch_obstacles_device(self, spheres, counts=None, dropped=None, wait_current_stream=True):
+        """qilqr_set_batch_obstacles_device on torch tensors: spheres (B, K, 8) float64 and counts int32 (B) or None, as set_batch_obstacles
+        takes them but on the solver's device, become the handle's per-problem table without the host; a used row with a non-finite word,
+        radius <= 0 or weight < 0 is dropped (the rows kept move up) and their number goes to dropped, int32 (1), when given.  ENQUEUED on
+        the solver's own stream and not waited for; clear_batch_obstacles() switches the table off again."""
+        if spheres is None or spheres.dim() != 3 or spheres.shape[2] != 8:
+            raise TypeError("spheres must be (B, K, 8)")
+        import torch
+        B, K = int(spheres.shape[0]), int(spheres.shape[1])
+        self._device_tensors(((spheres, "spheres", (B, K, 8)), (counts, "counts", (B,), torch.int32), (dropped, "dropped", (1,), torch.int32)))
+        if wait_current_stream:
+            self._wait_current_stream(spheres)
+        vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        _check(load().qilqr_set_batch_obstacles_device(self._h, vp(spheres), vp(counts), C.c_int32(B), C.c_int32(K), vp(dropped)))
 
     def profile_get(self):
         p = Profile()

@@ -177,6 +177,7 @@ void qilqr_destroy(qilqr_solver *s) {
   if (s->d_cl_q) (void)hipFree(s->d_cl_q);
   if (s->d_cov_image) (void)hipFree(s->d_cov_image);
   if (s->d_cov_out) (void)hipFree(s->d_cov_out);
+  if (s->d_fleet) (void)hipFree(s->d_fleet);
   if (s->d_consts) (void)hipFree(s->d_consts);
   if (s->h_counters) (void)hipHostFree(s->h_counters);
   if (s->h_active) (void)hipHostFree(s->h_active);
@@ -431,6 +432,8 @@ int qilqr_set_batch_obstacles(qilqr_solver *s, const double *spheres, const int3
   s->pobs_B = 0;
   s->pobs_K = s->pobs_max = 0;
   s->pobs_moving = false;
+  s->pobs_on_device = false;  // (the arrays below are this call's exact allocations: the device setter's capacities start again)
+  s->pobs_cap = s->pobs_counts_cap = 0;
   if (s->d_pobs) (void)hipFree(s->d_pobs);
   if (s->d_pobs_counts) (void)hipFree(s->d_pobs_counts);
   s->d_pobs = nullptr;

@@ -2,8 +2,9 @@
 // receding-horizon shift (k_shift: shift.hip), the backward pass over device arrays, the closed-loop flights of a plan (k_closed_loop and
 // k_closed_loop_scored: closed_loop.hip, closed_loop_scored.hip), the ends of the Monte-Carlo loop (monte_carlo.hip) and the risk
 // measures and the choice among candidate plans behind it (risk.hip), the sampling planner (mppi.hip, mppi_adapt.hip) and the linear
-// covariance analysis of a plan's closed loop (cov.hip; its rule is cov_launch.h's, its scratch the handle's).  Each call has
-// one refusal (from the rules of ranges.h and the six *_launch.h), one enqueue, a device form that enqueues and returns (on_device), and
+// covariance analysis of a plan's closed loop (cov.hip; its rule is cov_launch.h's, its scratch the handle's), and fleet deconfliction
+// with the device-side setter of the per-problem sphere table (fleet.hip; the rules are fleet_launch.h's).  Each call has
+// one refusal (from the rules of ranges.h and the seven *_launch.h), one enqueue, a device form that enqueues and returns (on_device), and
 // -- the shift and the flight -- a host form that stages the arrays through one DeviceScratch (enqueue_and_drain).  What the calls read of
 // the handle for a launch is read in one place each: sphere_tables, score_operands (the records are call_parts.h's).  Part of
 // ilqr_capi.hip's translation unit.
@@ -463,6 +464,67 @@ int qilqr_covariance_device(qilqr_solver *s, const qilqr_cov_rule *rule, const d
       if (!d_mean) go.d_mean = s->d_cov_out + knots * QILQR_COV;
     }
     return launched("k_cov_chain", launch_covariance(s->stream, s->consts, go));
+  });
+}
+}  // extern "C"
+
+// ---- fleet deconfliction: k_fleet_fit, k_fleet_pairs and k_fleet_select on the caller's device plans, and k_bob_set from the caller's
+// device table into the handle's (fleet_kernels.h, compiled by fleet.hip).  The rules are fleet_launch.h's; the handle gives its
+// stream, its step, the neighbours call's scratch and the setter's table.
+extern "C" {
+static_assert(QILQR_FLEET_MAX_NEIGHBOURS == FLEET_MAX_NEIGHBOURS && QILQR_FLEET_NBR == FLEET_NBR && QILQR_FLEET_SUMMARY == FLEET_SUMMARY &&
+                  QILQR_FLEET_COVER == FLEET_COVER && QILQR_FLEET_YIELD_TO_LOWER == FLEET_YIELD_TO_LOWER && sizeof(qilqr_fleet_rule) == 40,
+              "fleet_math.h, fleet_launch.h and the C header agree on the cap, the words of an entry and of a summary, the flags and the rule");
+int qilqr_fleet_neighbours_device(qilqr_solver *s, const qilqr_fleet_rule *rule, const double *d_plan, int32_t B, int32_t n, int32_t V, int32_t K,
+                                  double *d_summary, double *d_nbr, double *d_spheres, int32_t *d_counts) {
+  FleetCall call{};
+  call.rule = rule != nullptr;
+  if (rule) {
+    call.radius = rule->radius; call.weight = rule->weight; call.range = rule->range; call.conflict = rule->conflict;
+    call.flags = rule->flags;
+    call.reserved = rule->reserved;
+  }
+  call.plan = d_plan; call.summary = d_summary; call.nbr = d_nbr; call.spheres = d_spheres; call.counts = d_counts;
+  call.B = B; call.n = n; call.V = V; call.K = K;
+  call.handle = s != nullptr;
+  call.f32 = s && s->f32;
+  if (const char *why = fleet_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
+  return on_device(s, [&] {
+    if (int rc = cov_scratch(s, &s->d_fleet, &s->fleet_words, fleet_scratch(B, n, V, K).words, false)) return rc;
+    const FleetLaunch go{d_plan, s->d_fleet, B, n, V, K, s->consts.dt, *rule, d_summary, d_nbr, d_spheres, d_counts};
+    return launched("k_fleet_pairs", launch_fleet_neighbours(s->stream, go));
+  });
+}
+
+int qilqr_set_batch_obstacles_device(qilqr_solver *s, const double *d_spheres, const int32_t *d_counts, int32_t B, int32_t K, int32_t *d_dropped) {
+  const BobSetCall call{s != nullptr, s && s->f32, d_spheres, d_counts, d_dropped, B, K};
+  if (const char *why = bob_set_refusal(call)) return fail(QILQR_ERR_INVALID_ARG, why);
+  return on_device(s, [&] {
+    // the handle's table and counts, kept while they are large enough; what runs on the stream may still read the old ones
+    const size_t words = (size_t)bob_count(B, K);
+    if (s->pobs_cap < words || s->pobs_counts_cap < (size_t)B) {
+      HIP_TRY(hipStreamSynchronize(s->stream));
+      s->pobs_B = 0;  // (no table while the arrays are being replaced: a failure below leaves the handle without one)
+      s->pobs_K = s->pobs_max = 0;
+      s->pobs_moving = s->pobs_on_device = false;
+      s->pobs_cap = s->pobs_counts_cap = 0;
+      if (s->d_pobs) (void)hipFree(s->d_pobs);
+      if (s->d_pobs_counts) (void)hipFree(s->d_pobs_counts);
+      s->d_pobs = nullptr;
+      s->d_pobs_counts = nullptr;
+      HIP_TRY(hipMalloc((void **)&s->d_pobs, sizeof(double) * words));
+      HIP_TRY(hipMalloc((void **)&s->d_pobs_counts, sizeof(int32_t) * (size_t)B));
+      s->pobs_cap = words;
+      s->pobs_counts_cap = (size_t)B;
+    }
+    const BobSetLaunch go{d_spheres, d_counts, B, K, s->d_pobs, s->d_pobs_counts, d_dropped};
+    if (int rc = launched("k_bob_set", launch_bob_set(s->stream, go))) return rc;
+    s->pobs_B = B;
+    s->pobs_K = K;
+    s->pobs_max = 0;
+    s->pobs_moving = false;
+    s->pobs_on_device = true;
+    return (int)QILQR_OK;
   });
 }
 }  // extern "C"

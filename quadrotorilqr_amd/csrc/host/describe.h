@@ -40,7 +40,8 @@ int qilqr_describe(qilqr_solver *s, int32_t B, char *buf, size_t cap) {
   }
   if (s->pobs_B > 0)
     t += "; batch obstacles (extension): per-problem spheres for B = " + std::to_string(s->pobs_B) + " problems, K = " + std::to_string(s->pobs_K) +
-         ", at most " + std::to_string(s->pobs_max) + " used per problem, " + (s->pobs_moving ? "some moving" : "none moving") +
+         (s->pobs_on_device ? std::string(", set on the device (qilqr_set_batch_obstacles_device: the counts and whether a sphere moves are not known here)")
+                            : ", at most " + std::to_string(s->pobs_max) + " used per problem, " + (s->pobs_moving ? "some moving" : "none moving")) +
          ", penalised in the knot cost by k_linearize (the rounds never take the kernels that linearise inside themselves)" +
          (B != s->pobs_B ? " (a call of B = " + std::to_string(B) + " problems is refused)" : std::string());
   if (s->n_sched > 0)

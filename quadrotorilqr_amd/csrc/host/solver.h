@@ -72,6 +72,12 @@ struct qilqr_solver {
   bool pobs_moving = false;        // ... whether any used sphere has v != 0
   double *d_pobs = nullptr;        // ... the table in device memory, bob_count(pobs_B, pobs_K) doubles (obstacles.h, bob_index)
   int *d_pobs_counts = nullptr;    // ... and the counts, int32[pobs_B]
+  // ... set by qilqr_set_batch_obstacles_device: pobs_max and pobs_moving are unknown to the host (qilqr_describe says so), and the two
+  // arrays are kept between calls -- their capacities in doubles and in counts, 0 while the host setter's exact allocations stand
+  bool pobs_on_device = false;
+  size_t pobs_cap = 0, pobs_counts_cap = 0;
+  double *d_fleet = nullptr;       // qilqr_fleet_neighbours_device's scratch (fleet_launch.h: fleet_scratch), grown at the call that needs more
+  size_t fleet_words = 0;
   // the state-weight schedule (qilqr_set_state_weight_schedule): knot i of every problem takes Qs[i] for Q.  While it is set, `symmetric`,
   // `q_diag` and `layout` above are the schedule's (R and every Q_i symmetric; never diagonal; the dense kind 0) and the own_* fields keep
   // what qilqr_create derived from the handle's Q and R, for the clear

@@ -38,6 +38,7 @@
 #include "mppi_launch.h"
 #include "mppi_adapt_launch.h"
 #include "cov_launch.h"
+#include "fleet_launch.h"
 
 using namespace qilqr;
 

@@ -1,5 +1,5 @@
 // ranges.h -- the two questions every call on the caller's own arrays asks of their addresses before anything is launched: do two byte
-// ranges overlap, and does every array start on a 16-byte boundary.  Used by the rules of the six *_launch.h and by the shift's
+// ranges overlap, and does every array start on a 16-byte boundary.  Used by the rules of the seven *_launch.h and by the shift's
 // (host/caller_arrays.h); the records those calls share are call_parts.h's.  Host code only; compiles under g++ (the tests' harnesses).
 #pragma once
 

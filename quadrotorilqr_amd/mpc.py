@@ -16,7 +16,9 @@ under sampled disturbances -- and returns the statistics and the score of every 
 buffers.  Ahead of a solve, start / tick(..., explore=dict(S=, seed=, sigma=, lambda_=)) runs rounds of the sampling planner on the
 shifted plan (mppi_flight_device, mppi_update_device): the solve then polishes what the samples found.  With one more key,
 adapt=dict(rate=, floor=, cap=), the planner's spread is kept per plan, knot and rotor in `self.spread` (B, n, 4), adapted by every round
-(mppi_flight_spread_device, mppi_adapt_device) and shifted along the horizon with the plan.
+(mppi_flight_spread_device, mppi_adapt_device) and shifted along the horizon with the plan.  With deconflict=dict(radius=, weight=, K=, ...) the B plans are vehicles that share
+airspace: before its solve every vehicle gets its nearest partners' last plans as moving spheres (fleet_neighbours_device,
+set_batch_obstacles_device), on the device.
 """
 import numpy as np
 
@@ -56,6 +58,7 @@ class RecedingHorizon:
         self.spread = None               # the planner's spread (B, n, 4) while explore carries `adapt`: what the last round left
         self._spread_scratch = None      # ... and the buffer the next round writes
         self._held = None                # the shifted spread of a tick that was refused
+        self._fleet = None               # _deconflict()'s buffers for the last K: (K, summary (B, 8), nbr (B, K, 4), spheres (B, K, 8), counts (B), dropped (1))
 
     def _to_device(self, a, dst):
         import torch
@@ -139,18 +142,50 @@ class RecedingHorizon:
             self._mppi = (S, scratch, d_score, d_info)
         return d_info
 
-    def start(self, init, keep_init=False, gains=False, explore=None):
+    def _deconflict(self, deconflict):
+        """The plans in the current buffer -- every vehicle's latest intent -- as each other's obstacles, before their solve: the
+        neighbours of every vehicle as constant-velocity spheres (QuadrotorILQRBatch.fleet_neighbours_device) into buffers this object owns,
+        and those as the handle's per-problem sphere table (set_batch_obstacles_device).  Both enqueued on the solver's stream, behind
+        torch's current stream, and not waited for: the solve that follows is ordered behind them.  Returns (summary (B, 8), nbr (B, K, 4))."""
+        import torch
+        known = {"radius", "weight", "K", "fleet", "range", "conflict", "cover", "yield_to_lower"}
+        if not isinstance(deconflict, dict) or not {"radius", "weight", "K"} <= set(deconflict) or set(deconflict) - known:
+            raise TypeError("deconflict must be a dict with radius, weight, K and optionally fleet, range, conflict, cover, yield_to_lower")
+        K = int(deconflict["K"])
+        V = self.B if deconflict.get("fleet") is None else int(deconflict["fleet"])
+        if K <= 0 or K > capi.FLEET_MAX_NEIGHBOURS:
+            raise TypeError(f"deconflict: K must be 1 ... {capi.FLEET_MAX_NEIGHBOURS}")
+        if V <= 0 or self.B % V:
+            raise TypeError(f"deconflict: fleet must divide B = {self.B}")
+        if self._fleet is None or self._fleet[0] != K:
+            new = lambda *s, dtype=torch.float64: torch.zeros(s, dtype=dtype, device=self.device)
+            self._fleet = (K, new(self.B, capi.FLEET_SUMMARY), new(self.B, K, capi.FLEET_NBR), new(self.B, K, 8), new(self.B, dtype=torch.int32),
+                           new(1, dtype=torch.int32))
+        _, d_sum, d_nbr, d_sph, d_cnt, d_drop = self._fleet
+        self.solver.fleet_neighbours_device(self._buf[self._cur], V, K, deconflict["radius"], deconflict["weight"], range=deconflict.get("range", np.inf),
+                                            conflict=deconflict.get("conflict"), cover=deconflict.get("cover", False),
+                                            yield_to_lower=deconflict.get("yield_to_lower", False), summary=d_sum, nbr=d_nbr, spheres=d_sph, counts=d_cnt)
+        self.solver.set_batch_obstacles_device(d_sph, d_cnt, d_drop, wait_current_stream=False)
+        return d_sum, d_nbr
+
+    def _plan(self, keep_init, gains, explore, deconflict, steps=None):
+        """what start and tick do with the plan in the current buffer: the planner's rounds, the neighbours' spheres, the solve"""
+        info = None if explore is None else self._explore(explore, steps)
+        fleet = None if deconflict is None else self._deconflict(deconflict)
+        res = self._solve(keep_init, gains)
+        if info is not None:
+            res["explore"] = info
+        if fleet is not None:
+            res["separation"], res["neighbours"] = fleet
+        return res
+
+    def start(self, init, keep_init=False, gains=False, explore=None, deconflict=None):
         """A plain solve of `init` (B, n, 18; NumPy or torch) from the start of the handle's desired trajectory (horizon start 0).
-        gains=True, explore: as for tick."""
+        gains=True, explore, deconflict: as for tick."""
         self.solver.set_horizon_start(0)
         self.k0 = 0
         self._to_device(init, self._buf[self._cur])
-        if explore is None:
-            return self._solve(keep_init, gains)
-        info = self._explore(explore)
-        res = self._solve(keep_init, gains)
-        res["explore"] = info
-        return res
+        return self._plan(keep_init, gains, explore, deconflict)
 
     def control(self, x, i=0):
         """The (B, 4) controls of the last plan's feedback law at knot `i` for the measured states x (B, 13; NumPy or torch):
@@ -324,7 +359,7 @@ class RecedingHorizon:
         torch.cuda.current_stream(self.device).wait_event(self._stream.record_event())
         return dict(choice=d_choice, info=d_info, plan=d_plan, gains=d_gains, u0=d_plan[:, 0, 14:18])
 
-    def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False, gains=False, explore=None):
+    def tick(self, x0, steps=1, tail="hold", advance=True, keep_init=False, gains=False, explore=None, deconflict=None):
         """One control tick: the horizon start advanced by `steps` (advance=False: the desired trajectory is relative to the vehicle and
         stays), the last plan shifted into the other buffer with knot 0 at x0 (B, 13; NumPy or torch; None keeps the plan's own), and the
         solve from there.  Returns views (valid until the next tick but one) of the first controls u0 = traj[:, 0, 14:18], the plan, cost,
@@ -339,7 +374,19 @@ class RecedingHorizon:
         the result carries "explore", the last round's info (B, 8; QuadrotorILQRBatch.mppi_update_device's words).  With the key adapt =
         dict(rate=, floor=, cap=) the rounds adapt the spread per plan, knot and rotor (`self.spread`, (B, n, 4): set to sigma by start,
         shifted `steps` knots with a tail of sigma by every tick; mppi_flight_spread_device and mppi_adapt_device).  A tick that is refused -- steps or tail out of
-        range, or no window of n knots left behind the new start -- raises and leaves the object and the handle's start as they were."""
+        range, or no window of n knots left behind the new start -- raises and leaves the object and the handle's start as they were.
+        deconflict (None: nothing changes, bit for bit): a dict with radius, weight, K and optionally fleet (None: B, one fleet), range (inf),
+        conflict (None: radius), cover (False) and yield_to_lower (False) -- the B plans are vehicles in one world frame on one time base, rows b
+        with equal b // fleet sharing airspace.  Between the shift (and the planner's rounds, if any) and the solve, the K nearest partners
+        of every vehicle over the horizon become moving spheres of `radius` and `weight` (QuadrotorILQRBatch.fleet_neighbours_device on the
+        shifted plans, then set_batch_obstacles_device, on the solver's stream), and the result carries "separation", the (B, 8) summary
+        (smallest distance to a partner, its knot, its partner, partners closer than `conflict`, spheres written, largest radius), and
+        "neighbours", (B, K, 4): views of buffers this object owns.  This REPLACES the handle's per-problem sphere table (set_batch_obstacles),
+        and the table stays set afterwards: a later tick without deconflict still avoids the spheres of the last one that had it, until
+        clear_batch_obstacles().  Every vehicle avoids the others' PREVIOUS plans, not the ones this tick's solve produces: two vehicles that
+        meet head-on may both give way to the same side, tick after tick.  yield_to_lower is the remedy for such symmetric encounters --
+        a vehicle then avoids only partners in a smaller row, and row 0 of a fleet yields to nobody (prioritised planning).  A tick that is
+        refused after the table was set leaves the table set."""
         steps = int(steps)
         x0 = None if x0 is None else self._to_device(x0, self._x0)
         # (refuses steps or a tail out of range before anything of this object or of the handle has changed; the buffer it writes holds the
@@ -351,12 +398,7 @@ class RecedingHorizon:
                 self.solver.set_horizon_start(had_k0 + steps)
                 self.k0 = had_k0 + steps
             self._cur ^= 1
-            if explore is None:
-                return self._solve(keep_init, gains)
-            info = self._explore(explore, steps)
-            res = self._solve(keep_init, gains)
-            res["explore"] = info
-            return res
+            return self._plan(keep_init, gains, explore, deconflict, steps)
         except Exception:
             # a refused start or solve (past the end of the mission no window of n knots is left) leaves the last plan, its buffer and the
             # start it was solved at in force
